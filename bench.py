@@ -22,14 +22,27 @@ per GPU at N = 8 (the in-step xGMI all-reduce).  The total work per round is fix
 
 ``--path runner`` (default) times the PRODUCTION round loop,
 :func:`gfedntm_amd.federation.runner.run_distributed` -- what ``main.py
---backend rccl`` users get, with its per-round client bookkeeping -- and reports
-the engine-only replay loop of the same engine next to it
-(``engine_only_ms_per_step``).  ``--path engine`` times the bare replay loop.
+--backend rccl`` users get, with its per-round client bookkeeping.  ``--path engine``
+times the bare replay loop of the same engine instead.
 
 ``value`` = total training documents of all clients / round time.  Vocabulary
-consensus, init broadcast and the NPMI evaluation run outside the timed region;
-the NPMI comes from a SEPARATE untimed federation of ``--npmi-steps`` rounds
-(default 2000), so it does not depend on ``--steps``.
+consensus and init broadcast run outside the timed region.
+
+A plain run does only what the headline needs: set up, ``--warmup`` rounds, ``--steps``
+timed rounds, the result line.  ``--full`` adds every side measurement, each a run of
+its own after the timed rounds: the engine-only replay loop next to the runner's
+(``engine_only_ms_per_step``), the round split (the local steps alone / the collective
+detached), and the quality numbers -- NPMI (and client 1's TSS / DSS) from a SEPARATE
+untimed federation of ``--npmi-steps`` rounds (default 2000), so they do not depend on
+``--steps``.
+
+``--dump-outputs DIR`` writes what the timed rounds left behind, after the last of them:
+per client ``client<id>_state.npy`` (every float parameter and buffer of its model, the
+flat state the round loop updates in place; float32) and ``client<id>_loss.npy`` (the
+loss of its last timed step; float64).  An array over its share of 64 MB is cut down to
+a fixed, seeded sample of its elements.  The corpus, the initial weights and the
+training noise derive from ``--seed``, so two builds run with the same arguments get
+the same inputs.
 
 ``--sim-clients M`` (one GPU): M simulated clients in one process
 (:class:`LocalFederation`: all clients' steps + the in-process FedAvg kernel in
@@ -106,7 +119,13 @@ def parse(argv=None):
     p.add_argument("--npmi-steps", type=int, default=2000,
                    help="rounds of the separate untimed federation the NPMI is computed on "
                         "(0 = skip)")
-    p.add_argument("--no-npmi", action="store_true")
+    p.add_argument("--no-npmi", action="store_true",
+                   help="--full without the quality federation")
+    p.add_argument("--full", action="store_true",
+                   help="also run the side measurements (engine-only loop, round split, "
+                        "NPMI / TSS / DSS); a plain run times the rounds and nothing else")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write the state the timed rounds computed as DIR/<name>.npy")
     p.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"],
                    help="decoder GEMM operands (bf16: BASELINE config 'ProdLDA K=50 centralized "
                         "bf16' -- bf16 MFMA operands, fp32 accumulation, fp32 master weights and "
@@ -210,6 +229,32 @@ def _union_terms(sc, n_nodes):
 
 
 # ---------------------------------------------------------------------------
+# outputs of the timed rounds
+# ---------------------------------------------------------------------------
+DUMP_BUDGET_BYTES = 60 << 20          # all files of a run stay under 64 MB
+
+
+def _dump_outputs(args, clients, last_step: int, total: int):
+    """``--dump-outputs``: the state of this rank's clients after the last timed round
+    (call before anything else steps the engines).  ``total`` = clients of the whole
+    federation, every one of them gets the same share of the budget."""
+    if not args.dump_outputs:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // (4 * max(total, 1))          # float32 elements per client
+    torch.cuda.synchronize()
+    for c in clients:
+        state = c.tm.flat.buffer.detach().float().cpu().numpy().ravel()
+        if state.size > cap:
+            idx = np.sort(np.random.default_rng(12345).choice(state.size, cap, replace=False))
+            state = state[idx]
+        np.save(os.path.join(args.dump_outputs, f"client{c.id:02d}_state.npy"), state)
+        loss = c.tm.engine.loss_hist[last_step: last_step + 1].detach().cpu().numpy()
+        np.save(os.path.join(args.dump_outputs, f"client{c.id:02d}_loss.npy"),
+                loss.astype(np.float64))
+
+
+# ---------------------------------------------------------------------------
 # measurements
 # ---------------------------------------------------------------------------
 def _max_over_ranks(x: float, world: int) -> float:
@@ -306,17 +351,18 @@ def run_multi(args, rank, world, device, rehearse):
     eng = out["clients"][0].tm.engine
     n_rounds = args.warmup + args.steps
     final_loss = float(np.mean(eng.loss_hist[max(0, n_rounds - 20): n_rounds].cpu().numpy()))
-    # round split: the rank's batched local steps alone (no in-rank fold, no collective),
-    # replayed over the same plan steps after the run
+    _dump_outputs(args, out["clients"], n_rounds - 1, n_clients)
+    # round split (--full): the rank's batched local steps alone (no in-rank fold, no
+    # collective), replayed over the same plan steps after the run
     steps_ms = None
     rr = out["round"]
-    if hasattr(rr, "time_local_steps") and args.backend == "fused":
+    if args.full and hasattr(rr, "time_local_steps") and args.backend == "fused":
         steps_ms = rr.time_local_steps(args.warmup, min(args.steps, 500))
     # (every rank joins the reduction, also one that hosts a single client)
     steps_ms = _max_over_ranks(-1.0 if steps_ms is None else steps_ms, world)
     steps_ms = None if steps_ms < 0 else steps_ms
     rr.close()
-    # ---- quality: a separate untimed federation of --npmi-steps rounds (all clients) ----
+    # ---- quality (--full): a separate untimed federation of --npmi-steps rounds ----
     quality = _quality(args, corpora, ids, sc, n_clients, rank, device, kw)
     if rank == 0:
         ms = wall / max(out["timed_rounds"], 1) * 1e3
@@ -365,7 +411,7 @@ def _quality(args, corpora, ids, sc, n_clients, rank, device, kw) -> dict:
     """NPMI (top-10 words of client 1's topics over every client's documents) and client
     1's TSS / DSS against the generator's ground truth, from a separate untimed federation
     of --npmi-steps rounds, so the numbers do not depend on --steps."""
-    if args.no_npmi or args.npmi_steps <= 0:
+    if not args.full or args.no_npmi or args.npmi_steps <= 0:
         return {}
     from gfedntm_amd.federation.hierarchical import run_distributed_multi
     out = run_distributed_multi(corpora, ids, _params(args), _model_type(args),
@@ -427,13 +473,18 @@ def run_federated(args):
     dist.all_reduce(t, group=_ctrl_group())
     docs = float(t.item())                       # all clients' training documents
     ms_runner = wall / max(timed_rounds, 1) * 1e3
-    # ---- the same engine's bare replay loop (collective still attached) ----
+    if args.path != "engine":
+        _dump_outputs(args, [client], n_rounds - 1, world)
+    # ---- the same engine's bare replay loop (collective still attached): the headline of
+    # --path engine, a side measurement (--full) of --path runner ----
     engine_ms = engine_dev_ms = compute_ms = None
-    if args.backend == "fused":
+    if args.backend == "fused" and (args.full or args.path == "engine"):
         dt, ddev = _engine_loop(eng, args.warmup, n_rounds, world)
         engine_ms, engine_dev_ms = dt / args.steps * 1e3, ddev / args.steps * 1e3
         err = eng.fedavg_error()
-        if world > 1:
+        if args.path == "engine":
+            _dump_outputs(args, [client], n_rounds - 1, world)
+        if world > 1 and args.full:
             # round split: the same steps again with the collective detached
             saved = eng.detach_fedavg(close=False)
             _, ddev2 = _engine_loop(eng, args.warmup, n_rounds, world)
@@ -445,7 +496,7 @@ def run_federated(args):
     final_loss = float(np.mean(eng.loss_hist[max(0, n_rounds - 20): n_rounds].cpu().numpy()))
     if args.backend == "fused":
         eng.detach_fedavg()
-    # ---- quality: a separate untimed federation of a fixed number of rounds ----
+    # ---- quality (--full): a separate untimed federation of a fixed number of rounds ----
     quality = _quality(args, [corpus], [rank + 1], sc, world, rank, device,
                        {k: v for k, v in kw.items() if k not in ("params", "model_type")})
     npmi = quality.get("npmi")
@@ -510,8 +561,9 @@ def run_simulated(args):
     out = fed.run(timing_warmup=args.warmup)
     ms = out["wall_s"] / max(out["timed_rounds"], 1) * 1e3
     value = out["docs"] / out["wall_s"]
+    _dump_outputs(args, fed.clients, n_rounds - 1, M)
     npmi = None
-    if not args.no_npmi and args.npmi_steps > 0:
+    if args.full and not args.no_npmi and args.npmi_steps > 0:
         fed2 = LocalFederation(corpora, _params(args), _model_type(args), args.npmi_steps,
                                device=device, backend=args.backend, seed=args.seed,
                                graph=not args.no_graph, round_streams=not args.serial_clients)

@@ -8,10 +8,9 @@ server.py:270-279) and every client trains on its own field of study."""
 import os
 
 import numpy as np
-import pytest
 
-FIXTURE = "/root/reference/static/datasets/preprocessing_example/s2cs_tiny_preproc.parquet"
-pytestmark = pytest.mark.skipif(not os.path.exists(FIXTURE), reason="reference fixture absent")
+FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                       "s2cs_tiny_preproc.parquet")
 
 FOS = ["computer_science", "economics", "sociology", "political_science", "philosophy"]
 

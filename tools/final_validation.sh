@@ -2,6 +2,8 @@
 # Round-end evidence on the committed kernels: GPU tests, smoke, and one bench.py line
 # per BASELINE config (gpurun_out/final/*.jsonl).  Every GPU step has its own limit; the
 # first failure stops the script.
+# A plain bench.py run carries no side measurement: the records saved here have no engine-only
+# loop, local-steps split or NPMI unless a line passes --full (--no-npmi only trims --full).
 set -o pipefail
 o=gpurun_out/final
 mkdir -p "$o"
@@ -15,8 +17,8 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 280 --timeout
     -p no:cacheprovider > "$o/gpu_tests.log" 2>&1 || { tail -30 "$o/gpu_tests.log"; exit 1; }
 tail -n 1 "$o/gpu_tests.log" | tee "$o/gpu_tests.txt"
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -n 1 || exit 1
-run driver_default 200 --steps 20 --warmup 5
-run k50 200 --steps 2000 --warmup 200
+run driver_default 200 --full --steps 20 --warmup 5
+run k50 200 --full --steps 2000 --warmup 200
 run k50bf 200 --steps 2000 --warmup 200 --dtype bf16 --no-npmi
 run lda 200 --model LDA --steps 2000 --warmup 200 --no-npmi
 run ctm 200 --family ctm --topics 100 --steps 1000 --warmup 100 --no-npmi

@@ -1,6 +1,8 @@
 #!/bin/bash
 # Kernel-trace table of one bench.py configuration (no counters).
 # usage: tools/kt.sh <name> <bench.py args...>  ->  gpurun_out/kt_<name>/kernels.md
+# A plain bench.py run carries no side measurement: the records saved here have no engine-only
+# loop, local-steps split or NPMI unless a line passes --full (--no-npmi only trims --full).
 set -o pipefail
 name="$1"; shift
 out="gpurun_out/kt_$name"

@@ -3,6 +3,8 @@
 # usage: tools/profile_config.sh <name> <bench.py args...>
 # Writes gpurun_out/prof_<name>/{kernels.md,counters.md,bench.jsonl}.  Each rocprofv3
 # pass runs under its own time limit; a failing pass stops the script (no retries).
+# A plain bench.py run carries no side measurement: the records saved here have no engine-only
+# loop, local-steps split or NPMI unless a line passes --full (--no-npmi only trims --full).
 set -o pipefail
 name="$1"; shift
 out="gpurun_out/prof_$name"

@@ -10,7 +10,7 @@ run() {
   name="$1"; shift
   if [ "$mode" = bench ]; then
     echo "=== $name: $*"
-    timeout -k 10 420 python bench.py "$@" > "$out/$name.jsonl" 2> "$out/$name.err"
+    timeout -k 10 420 python bench.py --full "$@" > "$out/$name.jsonl" 2> "$out/$name.err"
     rc=$?
     tail -n 1 "$out/$name.jsonl" | cut -c1-220
   else
