@@ -446,6 +446,22 @@ __device__ __forceinline__ float randn(uint64_t seed, uint32_t step, uint32_t ta
   return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
 }
 
+// Box-Muller on both halves of one Philox draw of the RNG_INFER stream: four N(0, 1)
+// values (theta inference and held-out scoring draw the same normals: csrc/infer.hip,
+// csrc/score.hip).
+__device__ __forceinline__ void randn4(uint64_t seed, uint32_t ctr, uint32_t idx, float* n) {
+  const uint4 r = rng4(seed, ctr, RNG_INFER, idx);
+  const float u1 = ((float)(r.x >> 8) + 1.0f) * (1.0f / 16777216.0f);
+  const float u2 = u01(r.y);
+  const float u3 = ((float)(r.z >> 8) + 1.0f) * (1.0f / 16777216.0f);
+  const float u4 = u01(r.w);
+  const float ra = sqrtf(-2.0f * logf(u1)), rb = sqrtf(-2.0f * logf(u3));
+  float s2, c2, s4, c4;
+  sincospif(2.0f * u2, &s2, &c2);
+  sincospif(2.0f * u4, &s4, &c4);
+  n[0] = ra * c2; n[1] = ra * s2; n[2] = rb * c4; n[3] = rb * s4;
+}
+
 // Inverted-dropout scale: 0 with probability p, 1/(1-p) otherwise (torch semantics).
 __device__ __forceinline__ float drop_scale(uint64_t seed, uint32_t step, uint32_t tag,
                                             uint32_t idx, float p) {

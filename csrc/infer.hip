@@ -111,20 +111,6 @@ __device__ __forceinline__ void gather_doc(const int32_t* __restrict__ idx, cons
   }
 }
 
-// Box-Muller on both halves of one Philox draw: four N(0, 1) values.
-__device__ __forceinline__ void randn4(uint64_t seed, uint32_t ctr, uint32_t idx, float* n) {
-  const uint4 r = rng4(seed, ctr, RNG_INFER, idx);
-  const float u1 = ((float)(r.x >> 8) + 1.0f) * (1.0f / 16777216.0f);
-  const float u2 = u01(r.y);
-  const float u3 = ((float)(r.z >> 8) + 1.0f) * (1.0f / 16777216.0f);
-  const float u4 = u01(r.w);
-  const float ra = sqrtf(-2.0f * logf(u1)), rb = sqrtf(-2.0f * logf(u3));
-  float s2, c2, s4, c4;
-  sincospif(2.0f * u2, &s2, &c2);
-  sincospif(2.0f * u4, &s4, &c4);
-  n[0] = ra * c2; n[1] = ra * s2; n[2] = rb * c4; n[3] = rb * s4;
-}
-
 // NQ: input-layer outputs per lane (H0 <= 64 NQ); KQ: topics per lane (K <= 64 KQ).
 template <bool Staged, int NQ, int KQ, bool GB = false>
 __global__ void __launch_bounds__(INF_THREADS) gfk_theta_infer_k(GfkArgT<GB> ga, GfkInfer p) {

@@ -25,5 +25,11 @@ class AVITM(TopicModelBase):
         return self._loss(x, wd, pm, pv, mu, var, logvar)
 
     @torch.no_grad()
+    def _encode_rows(self, data: DeviceCSR, ids):
+        x = data.dense_rows(ids)
+        mu, logvar = self.model.inf_net(x)
+        return x, mu, logvar, None
+
+    @torch.no_grad()
     def _posterior(self, data: DeviceCSR, ids):
         return self.model.inf_net(data.dense_rows(ids))

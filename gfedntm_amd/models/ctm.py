@@ -54,6 +54,12 @@ class CTM(TopicModelBase):
         return loss
 
     @torch.no_grad()
+    def _encode_rows(self, data: DeviceCSR, ids):
+        x, ctx, lab = self._inputs(data, ids)
+        mu, logvar = self.model.inf_net(x, ctx, lab)
+        return x, mu, logvar, (lab if self.label_size else None)
+
+    @torch.no_grad()
     def _posterior(self, data: DeviceCSR, ids):
         x, ctx, lab = self._inputs(data, ids)
         return self.model.inf_net(x, ctx, lab)

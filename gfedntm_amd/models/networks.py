@@ -172,6 +172,11 @@ class _TopicDecoder(nn.Module):
 
     def _decode(self, mu, log_sigma):
         theta = F.softmax(self.reparameterize(mu, log_sigma), dim=1)
+        return self.decode_theta(theta)
+
+    def decode_theta(self, theta):
+        """(dropped-out theta, word distribution) of a given theta: the decoder without
+        the draw (scoring feeds explicit draws)."""
         theta = self.drop_theta(theta)
         if self.is_prodlda:
             word_dist = F.softmax(self.beta_batchnorm(theta @ self.beta), dim=1)

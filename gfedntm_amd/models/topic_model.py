@@ -172,6 +172,10 @@ class TopicModelBase:
             d["plan"] = plan
         if self.backend_fallback_reason:
             d["fused_unavailable"] = self.backend_fallback_reason
+        # held-out scoring (score / perplexity / validation) has its own coverage
+        d["score_engine"], why = self._score_engine()
+        if why:
+            d["score_fused_unavailable"] = why
         return d
 
     def _choose_backend(self, backend: str) -> str:
@@ -261,22 +265,134 @@ class TopicModelBase:
         total = self._run_plan(data, plan)
         return data.n_docs, total / data.n_docs
 
-    @torch.no_grad()
-    def _validate_epoch(self, loader_or_dataset):
+    def _validate_epoch(self, loader_or_dataset, seed: Optional[int] = None):
+        """Validation loss of one epoch: :meth:`score` with one draw per document (the
+        reference's estimator, avitm.py:295-321).  Fused backend: no dense rows, one
+        device-to-host copy."""
         ds = loader_or_dataset.dataset if hasattr(loader_or_dataset, "dataset") else \
             loader_or_dataset
-        data = self.device_data(ds)
-        was = self.model.training
-        self.model.eval()
-        total = 0.0
-        for a in range(0, data.n_docs, self.batch_size):
-            ids = torch.arange(a, min(a + self.batch_size, data.n_docs), device=self.device)
-            total += float(self._batch_loss(data, ids).item())
-        self.model.train(was)
-        return data.n_docs, total / max(data.n_docs, 1)
+        return len(ds), self.score(ds, n_samples=1, seed=seed)["loss"]
 
     def _batch_loss(self, data: DeviceCSR, ids):
         raise NotImplementedError
+
+    # ---------------------------------------------------------------- held-out scoring
+    def _score_engine(self):
+        """("fused", None), or ("torch", why the fused scorer does not cover this model)."""
+        from ..ops import engine as fused
+        try:
+            fused.score_supports(self, explain=True)
+            return "fused", None
+        except RuntimeError as e:
+            return "torch", str(e)
+
+    def _encode_rows(self, data: DeviceCSR, ids):
+        """(dense BoW rows, posterior mu, log sigma^2, label rows or None) of ``ids``."""
+        raise NotImplementedError
+
+    @torch.no_grad()
+    def _score_torch(self, data: DeviceCSR, n_samples: int, seed: int, eps=None):
+        """Per-document (KL, RL[, CE]) on the PyTorch modules in eval mode, from the CSR in
+        chunks of dense rows (never [D, V]).  ``eps``: explicit normals [n_samples, D, K]
+        instead of torch's generator, so two engines can be compared draw for draw."""
+        from .networks import reconstruction_terms
+        n, K, S = int(data.n_docs), self.n_components, int(n_samples)
+        model = self.model
+        gen = None
+        if eps is not None:
+            eps = torch.as_tensor(np.asarray(eps), dtype=torch.float32, device=self.device)
+            if tuple(eps.shape) != (S, n, K):
+                raise ValueError(f"eps must be [n_samples, D, K] = {(S, n, K)}")
+        elif S > 0:
+            gen = torch.Generator(device=self.device)
+            gen.manual_seed(int(seed))
+        chunk = max(1, min(4096, (1 << 24) // max(self.input_size, 1)))   # <= 64 MiB of dense rows
+        kls, rls, ces = [], [], []
+        was = model.training
+        model.eval()
+        for a in range(0, n, chunk):
+            ids = torch.arange(a, min(a + chunk, n), device=self.device)
+            x, mu, logvar, lab = self._encode_rows(data, ids)
+            kls.append(kl_terms(model.prior_mean, model.prior_variance, mu, torch.exp(logvar),
+                                logvar, K))
+            std = torch.exp(0.5 * logvar)
+            rl = torch.zeros_like(kls[-1])
+            ce = torch.zeros_like(rl) if lab is not None else None
+            for s in range(max(S, 1)):
+                if S == 0:
+                    z = mu
+                elif eps is not None:
+                    z = mu + eps[s, a:a + len(ids)] * std
+                else:
+                    z = mu + torch.randn(mu.shape, generator=gen, device=mu.device,
+                                         dtype=mu.dtype) * std
+                theta, wd = model.decode_theta(F.softmax(z, dim=1))
+                rl += reconstruction_terms(x, wd)
+                if ce is not None:
+                    ce += F.cross_entropy(model.label_classification(theta),
+                                          torch.argmax(lab, 1), reduction="none")
+            rls.append(rl / max(S, 1))
+            if ce is not None:
+                ces.append(ce / max(S, 1))
+        model.train(was)
+        if not kls:
+            z = torch.zeros(0, device=self.device)
+            return z, z, None
+        return torch.cat(kls), torch.cat(rls), (torch.cat(ces) if ces else None)
+
+    def score(self, dataset, n_samples: int = 1, seed: Optional[int] = None, eps=None,
+              engine: Optional[str] = None) -> dict:
+        """How well the model explains (held-out) documents: per-document ELBO terms, the
+        corpus loss and the perplexity.
+
+        ``kl`` / ``rl``: [D] arrays, the Gaussian KL of each document's posterior and its
+        reconstruction term, the mean over ``n_samples`` draws of theta (``n_samples=0``:
+        the plug-in theta = softmax(mu)); ``loss``: the mean over documents of
+        kl_weight * KL + RL, plus the label cross-entropy (the mean of every
+        ``batch_size`` documents, as the validation loop adds it) where the model has a
+        label head; ``perplexity``: exp(sum(KL + RL) / tokens); ``engine``: "fused"
+        (csrc/score.hip) or "torch" (the eval-mode modules; ``engine_info`` says why).
+        ``eps``: explicit normals [n_samples, D, K] -- PyTorch engine only; ``engine``
+        forces one of the two ("fused" raises where the kernels do not cover the model)."""
+        data = self.device_data(dataset)
+        if seed is None:
+            seed = int(torch.initial_seed()) % (2**31)
+        if engine not in (None, "fused", "torch"):
+            raise ValueError("engine must be None, 'fused' or 'torch'")
+        if engine == "fused":
+            if eps is not None:
+                raise ValueError("explicit eps runs on the PyTorch engine only")
+            from ..ops.engine import score_supports
+            score_supports(self, explain=True)
+        elif engine is None:
+            engine = "torch" if eps is not None else self._score_engine()[0]
+        ce = None
+        if engine == "fused":
+            klrl = self.engine.score(data, n_samples, seed=seed).cpu().numpy()
+            kl, rl = klrl[:, 0].copy(), klrl[:, 1].copy()
+        else:
+            kl, rl, ce = self._score_torch(data, n_samples, seed, eps)
+            packed = torch.stack([kl, rl] + ([ce] if ce is not None else []), 1).cpu().numpy()
+            kl, rl = packed[:, 0].copy(), packed[:, 1].copy()
+            ce = packed[:, 2].copy() if ce is not None else None
+        n = int(data.n_docs)
+        total = float(np.sum(float(self.weights.get("beta", 1)) * kl.astype(np.float64)
+                             + rl.astype(np.float64)))
+        if ce is not None:
+            B = self.batch_size
+            total += float(sum(ce[a:a + B].astype(np.float64).mean() for a in range(0, n, B)))
+        tokens = float(dataset.csr.sum())
+        elbo = float(np.sum(kl.astype(np.float64) + rl.astype(np.float64)))
+        out = {"kl": kl, "rl": rl, "loss": total / max(n, 1),
+               "perplexity": float(np.exp(elbo / tokens)) if tokens > 0 else float("nan"),
+               "engine": engine}
+        if ce is not None:
+            out["ce"] = ce
+        return out
+
+    def perplexity(self, dataset, n_samples: int = 1, seed: Optional[int] = None) -> float:
+        """exp(sum_d (KL_d + RL_d) / sum_d N_d) -- shorthand for :meth:`score`."""
+        return self.score(dataset, n_samples=n_samples, seed=seed)["perplexity"]
 
     def fit(self, train_dataset, validation_dataset=None, save_dir=None, patience=5, delta=0,
             n_samples=20):

@@ -126,6 +126,25 @@ def supports(tm, explain: bool = False) -> bool:
     return _explain(need <= LDS_LIMIT, f"LDS budget exceeded ({need} B)", explain)
 
 
+def score_supports(tm, explain: bool = False) -> bool:
+    """Whether held-out scoring of this model runs on the fused kernels (csrc/score.hip:
+    the eval-mode ProdLDA decoder -- AVITM, CombinedTM, ZeroShotTM without a label head)."""
+    checks = [
+        (getattr(tm, "backend", None) == "fused", "the model runs on the PyTorch engine"),
+        (tm.model_type.lower() == "prodlda",
+         "NeuralLDA scoring is a sparse-only problem (theta . softmax(beta) at the non-zeros): "
+         "no hand-written scorer yet"),
+        (not getattr(tm, "label_size", 0), "label-head models add a classifier cross-entropy"),
+        (tm.n_components <= 512, "n_components > 512"),
+    ]
+    for ok, why in checks:
+        if not ok:
+            if explain:
+                raise RuntimeError(f"fused scoring unsupported: {why}")
+            return False
+    return True
+
+
 UPDATE_GRAD, UPDATE_FUSED = 0, 1
 
 
@@ -1274,34 +1293,99 @@ class FusedEngine(EngineBase):
         threshold + L1 normalisation (federated_model.py:170-173); ``moments`` returns
         the posterior [D, 2, K] = (mu, log sigma^2) instead.  The draws are keyed by
         (seed, document index), so the chunking does not change the result."""
-        m, K, n = self._m, int(self._m.K), int(data.n_docs)
+        K, n = int(self._m.K), int(data.n_docs)
         out = torch.empty(n, 2 * K if moments else K, dtype=torch.float32, device=self.device)
         if n:
-            ctx = m.input != abi.IN_BOW
-            if ctx and data.contextual is None:
-                raise RuntimeError("CTM inference needs the contextual embeddings")
-            if chunk is None:       # the CombinedTM adapt_bert output is [chunk, V]: <= 1 GiB
-                chunk = (1 << 16) if not ctx else max(256, min(1 << 16, (1 << 28) // max(m.V, 1)))
-            cu = torch.cuda.get_device_properties(self.device).multi_processor_count
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+            if chunk is None:
+                chunk = self._infer_chunk()
+            flags = (abi.INFER_POSTPROCESS if postprocess else 0) | \
+                (abi.INFER_MOMENTS if moments else 0)
             for d0 in range(0, n, chunk):
                 d1 = min(n, d0 + chunk)
-                hctx = self._ctx_dense(data, d0, d1).contiguous() if ctx else None
-                p = abi.GfkInfer()
-                p.indptr = data.indptr.data_ptr() + 4 * d0
-                p.indices, p.values = data.indices.data_ptr(), data.values.data_ptr()
-                p.hctx = hctx.data_ptr() if hctx is not None else None
-                p.out = out.data_ptr() + 4 * d0 * out.shape[1]
-                p.n_docs, p.n_samples = d1 - d0, int(n_samples)
-                p.flags = (abi.INFER_POSTPROCESS if postprocess else 0) | \
-                    (abi.INFER_MOMENTS if moments else 0)
-                p.thr, p.seed, p.doc0 = float(threshold), int(seed) % (1 << 64), d0
-                p.grid = int(max(1, min(-(-(d1 - d0) // 8), 4 * cu)))   # 8 waves (docs) per WG
-                self._sync_dev()
-                rc = self.lib.gfk_theta_infer(C.byref(m), C.byref(p), stream)
-                if rc:
-                    raise RuntimeError(f"gfk_theta_infer failed ({rc})")
+                self._infer_launch(data, d0, d1, out.data_ptr() + 4 * d0 * out.shape[1],
+                                   n_samples, flags, threshold, seed)
         return out.view(n, 2, K) if moments else out
+
+    def _infer_chunk(self) -> int:
+        """Default documents per inference launch (the CombinedTM adapt_bert output is
+        [chunk, V]: <= 1 GiB)."""
+        if self._m.input == abi.IN_BOW:
+            return 1 << 16
+        return max(256, min(1 << 16, (1 << 28) // max(int(self._m.V), 1)))
+
+    def _infer_launch(self, data: DeviceCSR, d0: int, d1: int, out_ptr: int, n_samples: int,
+                      flags: int, threshold: float, seed: int):
+        """One gfk_theta_infer launch over documents [d0, d1) into ``out_ptr``."""
+        m = self._m
+        ctx = m.input != abi.IN_BOW
+        if ctx and data.contextual is None:
+            raise RuntimeError("CTM inference needs the contextual embeddings")
+        cu = torch.cuda.get_device_properties(self.device).multi_processor_count
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        hctx = self._ctx_dense(data, d0, d1).contiguous() if ctx else None
+        p = abi.GfkInfer()
+        p.indptr = data.indptr.data_ptr() + 4 * d0
+        p.indices, p.values = data.indices.data_ptr(), data.values.data_ptr()
+        p.hctx = hctx.data_ptr() if hctx is not None else None
+        p.out = out_ptr
+        p.n_docs, p.n_samples = d1 - d0, int(n_samples)
+        p.flags = flags
+        p.thr, p.seed, p.doc0 = float(threshold), int(seed) % (1 << 64), d0
+        p.grid = int(max(1, min(-(-(d1 - d0) // 8), 4 * cu)))   # 8 waves (docs) per WG
+        self._sync_dev()
+        rc = self.lib.gfk_theta_infer(C.byref(m), C.byref(p), stream)
+        if rc:
+            raise RuntimeError(f"gfk_theta_infer failed ({rc})")
+
+    @torch.no_grad()
+    def score(self, data: DeviceCSR, n_samples: int = 1, seed: int = 0,
+              chunk: Optional[int] = None) -> torch.Tensor:
+        """Held-out ELBO terms [D, 2] = (KL, RL) of every document of ``data``
+        (csrc/score.hip): the eval-mode encoder once per document (gfk_theta_infer, the
+        posterior moments), then the eval-mode ProdLDA decoder over ``n_samples`` draws of
+        theta = softmax(mu + eps * sigma) per document -- the normals of ``theta_infer``
+        for the same seed; ``n_samples=0`` scores the plug-in theta = softmax(mu).  RL is
+        the mean over the draws, KL is exact.  Always fp32.  No dense [rows, V] matrix is
+        built and nothing is read back: the result stays on the device.  Draws are keyed by
+        (seed, document index), so neither the chunking nor the grid changes the result."""
+        score_supports(self.tm, explain=True)
+        m, K, n, S = self._m, int(self._m.K), int(data.n_docs), int(n_samples)
+        if S < 0:
+            raise ValueError("n_samples must be >= 0")
+        R = max(S, 1)
+        out = torch.empty(n, 2, dtype=torch.float32, device=self.device)
+        if not n:
+            return out
+        if chunk is None:       # <= 64 Ki rows of theta per launch
+            chunk = max(64, min(self._infer_chunk(), (1 << 16) // R))
+        if int(data.vocab_size) != int(m.V):
+            raise ValueError(f"data has {data.vocab_size} columns, the model {int(m.V)}")
+        f = dict(dtype=torch.float32, device=self.device)
+        rows = min(n, chunk) * R
+        mom = torch.empty(min(n, chunk), 2 * K, **f)
+        theta = torch.empty(rows, K, **f)
+        rl_rows = torch.empty(rows, **f)
+        nv = int(self.lib.gfk_score_vranges(C.byref(m)))    # vocabulary ranges per row block
+        lse_part = torch.empty(nv * rows * 2, **f)
+        cu = torch.cuda.get_device_properties(self.device).multi_processor_count
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        block = 64 if K <= 256 else 32                  # rows per workgroup (csrc/score.hip)
+        wg_per_cu = max(1, min(4, LDS_LIMIT // max(int(self.lib.gfk_doc_score_smem(C.byref(m))), 1)))
+        for d0 in range(0, n, chunk):
+            d1 = min(n, d0 + chunk)
+            self._infer_launch(data, d0, d1, mom.data_ptr(), 1, abi.INFER_MOMENTS, 0.0, seed)
+            p = abi.GfkScore()
+            p.indptr = data.indptr.data_ptr() + 4 * d0
+            p.indices, p.values = data.indices.data_ptr(), data.values.data_ptr()
+            p.moments, p.theta, p.lse_part = mom.data_ptr(), theta.data_ptr(), lse_part.data_ptr()
+            p.rl_rows, p.out = rl_rows.data_ptr(), out.data_ptr() + 8 * d0
+            p.n_docs, p.n_samples = d1 - d0, S
+            p.seed, p.doc0 = int(seed) % (1 << 64), d0
+            p.grid = int(max(1, min(-(-(d1 - d0) * R // block) * nv, wg_per_cu * cu)))
+            rc = self.lib.gfk_doc_score(C.byref(m), C.byref(p), stream)
+            if rc:
+                raise RuntimeError(f"gfk_doc_score failed ({rc})")
+        return out
 
     # ------------------------------------------------------------------ step
     def _launch(self, phases):

@@ -166,6 +166,14 @@ class GfkInfer(C.Structure):
 INFER_POSTPROCESS, INFER_MOMENTS = 1, 2
 
 
+class GfkScore(C.Structure):
+    """held-out scoring launch (csrc/score.hip)."""
+    _fields_ = [("indptr", P), ("indices", P), ("values", P), ("moments", P), ("theta", P),
+                ("lse_part", P), ("rl_rows", P), ("out", P),
+                ("n_docs", C.c_int32), ("n_samples", C.c_int32), ("seed", C.c_uint64),
+                ("grid", C.c_int32), ("doc0", C.c_int32)]
+
+
 FOLD_W, FOLD_V = 8, 16
 
 
@@ -227,6 +235,15 @@ def declare(lib: C.CDLL) -> None:
     lib.gfk_infer_struct_size.restype = C.c_size_t
     if lib.gfk_infer_struct_size() != C.sizeof(GfkInfer):
         raise RuntimeError("GfkInfer ABI mismatch")
+    lib.gfk_score_struct_size.restype = C.c_size_t
+    if lib.gfk_score_struct_size() != C.sizeof(GfkScore):
+        raise RuntimeError("GfkScore ABI mismatch")
+    lib.gfk_doc_score.argtypes = [C.POINTER(GfkModel), C.POINTER(GfkScore), C.c_void_p]
+    lib.gfk_doc_score.restype = C.c_int
+    lib.gfk_doc_score_smem.argtypes = [C.POINTER(GfkModel)]
+    lib.gfk_doc_score_smem.restype = C.c_size_t
+    lib.gfk_score_vranges.argtypes = [C.POINTER(GfkModel)]
+    lib.gfk_score_vranges.restype = C.c_int
     if hasattr(lib, "gfk_fold_struct_size"):
         lib.gfk_fold_struct_size.restype = C.c_size_t
         lib.gfk_fold_client_struct_size.restype = C.c_size_t
