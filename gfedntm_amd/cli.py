@@ -76,6 +76,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--stop_at_num_epochs", action="store_true")
     p.add_argument("--metrics_every", type=int, default=0,
                    help="JSONL metrics window (rounds) in <logs>/metrics_<date>.jsonl; 0 = end only")
+    p.add_argument("--npmi_topk", type=int, default=0,
+                   help="local/rccl/gloo: after training, the NPMI coherence of the global model's "
+                        "top-N words over every client's documents (integer co-occurrence counts "
+                        "are summed; the documents stay with their client); 0 = off")
     p.add_argument("--collective_timeout", type=float, default=1800.0,
                    help="rccl/gloo: process-group timeout in seconds (failed collectives abort)")
     p.add_argument("--heartbeat_timeout", type=float, default=120.0,
@@ -153,7 +157,13 @@ def run_local(args, cfg) -> dict:
         checkpoint_every=args.checkpoint_every if args.checkpoint_every is not None
         else cfg.checkpoint_every, stamp=stamp, agg=args.agg,
         fedavg_wire=args.fedavg_wire or cfg.fedavg_wire)
-    return fed.run()
+    out = fed.run()
+    if args.npmi_topk > 0:
+        from .federation.runner import log_coherence
+        coh = fed.coherence(topk=args.npmi_topk)
+        log_coherence(logger, coh, args.npmi_topk)
+        out.update(npmi=coh["npmi"], npmi_topk=args.npmi_topk, topic_diversity=coh["diversity"])
+    return out
 
 
 def _rank_main(args, cfg) -> dict:
@@ -190,7 +200,8 @@ def _rank_main(args, cfg) -> dict:
         else cfg.checkpoint_every, stamp=stamp,
         metrics_path=os.path.join(f"{logs_client}{ids[0]}", f"metrics_{stamp}.jsonl"),
         metrics_every=args.metrics_every, heartbeat_timeout=args.heartbeat_timeout,
-        agg_mode=args.agg, client_ids=ids, fedavg_wire=args.fedavg_wire or cfg.fedavg_wire)
+        agg_mode=args.agg, client_ids=ids, fedavg_wire=args.fedavg_wire or cfg.fedavg_wire,
+        coherence_topk=args.npmi_topk)
 
 
 def _spawned(local_rank: int, world: int, port: int, argv: List[str]):
@@ -232,6 +243,11 @@ def main(argv: Optional[List[str]] = None):
         parser.error("start_client needs --id >= 1 (0 is the server)")
     if args.command == "start_server" and args.id != 0:
         parser.error("start_server runs with --id 0")
+    if args.npmi_topk < 0:
+        parser.error("--npmi_topk must be >= 0")
+    if args.npmi_topk > 0 and args.backend == "grpc":
+        raise SystemExit("--npmi_topk needs a collective backend (local / rccl / gloo): the "
+                         "reference wire protocol has no message for co-occurrence counts")
     from .utils.config import load_config
     cfg = load_config(args.config)
     if args.matmul_dtype is not None:

@@ -9,7 +9,10 @@
   probabilities estimated from document co-occurrence in a reference corpus
   (bag-of-words data has no word order, so there is no sliding window).  The
   co-occurrence counts are one GEMM on the device: D_bin[:, W]^T D_bin[:, W]
-  over the union W of all topics' top words.
+  over the union W of all topics' top words (``npmi_coherence``).  The counts are
+  integers, so they can also be taken exactly where the documents are -- on a device CSR
+  (csrc/cooc.hip) or a host CSR, per client -- and summed: ``cooccurrence_counts``,
+  ``federated_cooccurrence``, ``npmi_from_counts`` (the same float64 formula).
 * Topic diversity (TD) and rank-biased overlap (RBO) -- tm_wrapper.py:386-400.
 * Word-mover's distance between topic sets given word vectors -- aux_scripts/evaluation/wmd.py.
 """
@@ -60,6 +63,14 @@ def npmi_coherence(topics: Sequence[Sequence[int]], corpus: sp.csr_matrix, eps: 
     dev = torch.device(device) if device is not None else torch.device("cpu")
     d = torch.from_numpy(sub.toarray()).to(dev)
     co = (d.t() @ d).double() / n_docs          # P(wi, wj); diagonal = P(wi)
+    scores = _npmi_scores(topics, pos, co, eps, dev)
+    return scores if per_topic else float(np.mean(scores))
+
+
+def _npmi_scores(topics, pos, co, eps, dev) -> List[float]:
+    """Per-topic NPMI from the float64 joint probabilities ``co`` [W, W] (diagonal = P(wi));
+    ``pos`` maps a word to its row.  The one body behind :func:`npmi_coherence` and
+    :func:`npmi_from_counts`."""
     p = torch.diagonal(co)
     scores = []
     for t in topics:
@@ -70,7 +81,146 @@ def npmi_coherence(topics: Sequence[Sequence[int]], corpus: sp.csr_matrix, eps: 
         npmi = pmi / (-torch.log(pij + eps))
         iu = torch.triu_indices(len(t), len(t), 1, device=dev)
         scores.append(float(npmi[iu[0], iu[1]].mean().item()))
+    return scores
+
+
+def npmi_from_counts(topics: Sequence[Sequence[int]], words: Sequence[int], counts, n_docs: int,
+                     eps: float = 1e-12, per_topic: bool = False):
+    """:func:`npmi_coherence` from exact integer document co-occurrence counts:
+    ``counts[i][j]`` = documents holding both ``words[i]`` and ``words[j]`` (the diagonal is
+    the document frequency), out of ``n_docs``.  The same float64 formula, on the CPU; with
+    the counts of the same corpus the result is bit-identical to :func:`npmi_coherence`."""
+    topics = [list(map(int, t)) for t in topics]
+    if torch.is_tensor(words):
+        words = words.detach().cpu().tolist()
+    pos = {int(w): i for i, w in enumerate(words)}
+    dev = torch.device("cpu")
+    c = counts.detach().to(dev) if torch.is_tensor(counts) else torch.from_numpy(np.asarray(counts))
+    co = c.double() / n_docs
+    scores = _npmi_scores(topics, pos, co, eps, dev)
     return scores if per_topic else float(np.mean(scores))
+
+
+def _word_tensor(words, vocab_size: int) -> torch.Tensor:
+    """``words`` as an int64 tensor (kept on its device when it is one); distinct indices in
+    [0, vocab_size) or ValueError."""
+    if torch.is_tensor(words):
+        w = words.detach().reshape(-1)
+        if w.dtype.is_floating_point or w.dtype == torch.bool:
+            raise ValueError("words must be integer vocabulary indices")
+        w = w.long()
+    else:
+        w = torch.from_numpy(np.asarray(list(words), dtype=np.int64).reshape(-1))
+    if w.numel():
+        if int(w.min()) < 0 or int(w.max()) >= vocab_size:
+            raise ValueError(f"words must be vocabulary indices in [0, {vocab_size})")
+        if int(torch.unique(w).numel()) != int(w.numel()):
+            raise ValueError("words must be distinct")
+    return w
+
+
+def _host_csr(data) -> sp.csr_matrix:
+    if sp.issparse(data):
+        return sp.csr_matrix(data)
+    return sp.csr_matrix((data.values.cpu().numpy(), data.indices.cpu().numpy(),
+                          data.indptr.cpu().numpy()), shape=(data.n_docs, data.vocab_size))
+
+
+def _cooccurrence(data, words, engine: Optional[str], chunk: Optional[int]):
+    """(counts, engine used) -- :func:`cooccurrence_counts` plus which implementation ran."""
+    from ..data.bow import DeviceCSR
+    from ..ops import cooc
+    if engine not in (None, "fused", "exact"):
+        raise ValueError("engine must be None, 'fused' or 'exact'")
+    if not (isinstance(data, DeviceCSR) or sp.issparse(data)):
+        raise TypeError("data must be a DeviceCSR or a scipy sparse matrix")
+    on_device = isinstance(data, DeviceCSR)
+    vocab_size = int(data.vocab_size if on_device else data.shape[1])
+    w = _word_tensor(words, vocab_size)
+    device = data.device if on_device else torch.device("cpu")
+    if engine == "fused":
+        if not on_device:
+            if not torch.cuda.is_available():
+                raise RuntimeError("engine='fused' needs a GPU")
+            data = DeviceCSR(data, torch.device("cuda", torch.cuda.current_device()))
+            device = data.device
+        elif device.type != "cuda":
+            raise RuntimeError("engine='fused' needs the data on a GPU")
+    elif engine is None and on_device and device.type == "cuda":
+        # on a GPU the kernels are the path: a missing library raises, only a word list past
+        # their limit goes to the host (and says so)
+        if int(w.numel()) <= cooc.max_words():
+            engine = "fused"
+        else:
+            import logging
+            logging.getLogger("gfedntm_amd").info(
+                "co-occurrence counts: %d words exceed the kernels' %d, using the host product",
+                int(w.numel()), cooc.max_words())
+    if engine == "fused":
+        return cooc.counts(data, w.to(device), chunk), "fused"
+    if chunk is not None and int(chunk) < 1:
+        raise ValueError("chunk must be a positive number of documents")
+    xb = (_host_csr(data)[:, w.cpu().numpy()] > 0).astype(np.int64)
+    co = np.asarray((xb.T @ xb).todense(), dtype=np.int64).reshape(len(w), len(w))
+    return torch.from_numpy(co).to(device), "exact"
+
+
+def cooccurrence_counts(data, words: Sequence[int], engine: Optional[str] = None,
+                        chunk: Optional[int] = None) -> torch.Tensor:
+    """Exact document co-occurrence counts of ``words`` in ``data``: int64 [W, W] on the
+    data's device, ``[i][j]`` = documents in which ``words[i]`` and ``words[j]`` both have a
+    stored value > 0 (diagonal: document frequency).
+
+    ``data``: a :class:`~gfedntm_amd.data.bow.DeviceCSR` or a scipy sparse matrix; ``words``:
+    distinct vocabulary indices in any order.  ``engine``: "fused" -- the bit-matrix kernels
+    of csrc/cooc.hip on the device CSR (raises off-GPU, without the kernel library, or past
+    the kernels' word limit); "exact" -- the sparse integer product Xb^T Xb on the host
+    (scipy; no dense [D, W] either); None -- fused for a DeviceCSR on a GPU within the
+    limit, exact otherwise.  ``chunk``: documents per launch of the fused path (any positive
+    number; by default the bit matrix stays at or below 256 MiB).  The counts are integers:
+    neither engine, chunking nor grid changes them."""
+    return _cooccurrence(data, words, engine, chunk)[0]
+
+
+def _federated_cooccurrence(datas, words, group=None, engine: Optional[str] = None):
+    datas = list(datas)
+    counts, n_docs, engines = None, 0, []
+    for d in datas:
+        c, e = _cooccurrence(d, words, engine, None)
+        counts = c if counts is None else counts + c.to(counts.device)
+        n_docs += int(d.n_docs if hasattr(d, "n_docs") else d.shape[0])
+        engines.append(e)
+    if counts is None:
+        nw = int(words.numel()) if torch.is_tensor(words) else len(list(words))
+        counts = torch.zeros(nw, nw, dtype=torch.int64)
+    import torch.distributed as dist
+    if group is not False and (group is not None or (dist.is_available() and dist.is_initialized())):
+        shape, dev = counts.shape, counts.device
+        buf = torch.cat([counts.reshape(-1), torch.tensor([n_docs], dtype=torch.int64, device=dev)])
+        # gloo reduces host tensors, RCCL device tensors: stage the (small) buffer where the
+        # group's backend wants it
+        backend = str(dist.get_backend(group))
+        if backend == "gloo" and buf.is_cuda:
+            buf = buf.cpu()
+        elif backend == "nccl" and not buf.is_cuda:
+            buf = buf.cuda()
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
+        buf = buf.to(dev)
+        counts, n_docs = buf[:-1].reshape(shape), int(buf[-1])
+    used = "fused" if engines and all(e == "fused" for e in engines) else "exact"
+    return counts, n_docs, used
+
+
+def federated_cooccurrence(datas, words: Sequence[int], group=None):
+    """(counts int64 [W, W], n_docs) of the union of document shards that stay where they
+    are: :func:`cooccurrence_counts` of each of this process's ``datas`` summed, then -- when
+    ``group`` is a process group, or a default group is initialised and ``group`` is not
+    False -- one ``all_reduce(SUM)`` of the matrix and the document count over the ranks.
+    Integer sums do not depend on their order, so the result equals the counts of the
+    stacked corpus exactly; only W^2 + 1 integers leave a process.  ``words`` must be the
+    same list on every rank."""
+    counts, n_docs, _ = _federated_cooccurrence(datas, words, group)
+    return counts, n_docs
 
 
 def topic_diversity(topics: Sequence[Sequence], topk: int = 25) -> float:

@@ -115,6 +115,25 @@ def record_terms(clients, on: bool):
             c.tm.engine.record_terms(True)
 
 
+def federation_coherence(tm, datas, topk: int = 10, matrix: str = "beta", per_topic: bool = False,
+                         group=False, n_clients: Optional[int] = None) -> Dict:
+    """NPMI of ``tm``'s topics over document shards ``datas`` (and, with a process group,
+    over every rank's): only the [W, W] integer counts and the document count are summed
+    (eval/metrics.py federated_cooccurrence), NPMI is evaluated once in float64."""
+    from ..eval.metrics import _federated_cooccurrence
+    topics = tm.top_word_indices(topk, matrix)
+    words = torch.unique(topics)
+    counts, n_docs, engine = _federated_cooccurrence(datas, words, group)
+    out = tm._coherence_result(topics, words, counts, n_docs, engine, topk, per_topic)
+    out["clients"] = len(datas) if n_clients is None else int(n_clients)
+    return out
+
+
+def log_coherence(logger, coh: Dict, topk: int):
+    logger.info("-- -- Global NPMI@%d: %.4f (TD %.4f, %d documents, %d clients)", topk,
+                float(np.mean(coh["per_topic"])), coh["diversity"], coh["n_docs"], coh["clients"])
+
+
 class LocalFederation:
     """N clients in one process; the shared state is averaged exactly after every round."""
 
@@ -440,6 +459,16 @@ class LocalFederation:
         if self.save_server:
             self.save_global(server_model_path(self.save_server, self.stamp))
 
+    def coherence(self, topk: int = 10, matrix: str = "beta", per_topic: bool = False) -> Dict:
+        """NPMI of the global model on the union of the clients' documents, which stay in
+        their shards: the topics come from ``clients[0].tm`` (after a round every client
+        holds the same state), the integer co-occurrence counts from every client's device
+        CSR (already in the consensus vocabulary), summed.  The keys of
+        ``TopicModelBase.coherence`` plus ``clients``; equal to the coherence on the stacked
+        corpus exactly."""
+        return federation_coherence(self.clients[0].tm, [c.data for c in self.clients], topk,
+                                    matrix, per_topic, group=False, n_clients=len(self.clients))
+
     def save_global(self, path: str):
         """The global model = the averaged state (B4/B5); betas only, like the reference."""
         tm = self.clients[0].tm
@@ -474,7 +503,8 @@ def run_distributed(corpus, params: Dict, model_type: str = "avitm",
                     agg_mode: str = "params", timing_warmup: int = 0,
                     rehearse_1gpu: Optional[bool] = None, allreduce: Optional[str] = None,
                     round_hook=None, client_ids: Optional[Sequence[int]] = None,
-                    keep_round: bool = False, fedavg_wire: str = "fp32") -> Dict:
+                    keep_round: bool = False, fedavg_wire: str = "fp32",
+                    coherence_topk: int = 0) -> Dict:
     """Runs this process's client(s); torch.distributed must be initialised (RANK /
     WORLD_SIZE).  ``corpus`` is this rank's one client (id rank + 1), or a list of client
     corpora with their ids ``client_ids`` -- a contiguous block of a federation of more
@@ -522,7 +552,13 @@ def run_distributed(corpus, params: Dict, model_type: str = "avitm",
 
     ``keep_round``: leave the rank's data plane attached after the run (the caller closes
     ``out["round"]``; bench.py times the bare engine loop on it); by default it is
-    released before returning, on success or error."""
+    released before returning, on success or error.
+
+    ``coherence_topk`` > 0: after the last round every rank counts the document
+    co-occurrences of the global model's top words on its clients' shards, the ranks
+    all-reduce the integer counts once over the control plane, and the result gains
+    ``npmi``, ``npmi_topk`` and ``topic_diversity`` (identical on every rank; the documents
+    stay where they are).  0: no extra collective, no extra keys."""
     import torch.distributed as dist
     from .hierarchical import agree_client_map
     from .rank_round import MultiClientRound, SingleClientRound
@@ -613,6 +649,13 @@ def run_distributed(corpus, params: Dict, model_type: str = "avitm",
                           max_iters, stop_at_num_epochs, checkpoint_dir, checkpoint_every,
                           metrics, metrics_every, timing_warmup, round_hook, agg_mode,
                           save_server, stamp)
+        if coherence_topk > 0:
+            coh = federation_coherence(clients[0].tm, [c.data for c in clients], coherence_topk,
+                                       group=ctrl, n_clients=len(every))
+            if rank == 0:
+                log_coherence(logger, coh, coherence_topk)
+            out.update(npmi=coh["npmi"], npmi_topk=int(coherence_topk),
+                       topic_diversity=coh["diversity"])
         ok = True
         return out
     finally:

@@ -505,6 +505,54 @@ class TopicModelBase:
         _, idxs = torch.topk(comps.detach(), k, dim=1)
         return [[idx2token[int(i)] for i in row] for row in idxs.cpu().numpy()]
 
+    @torch.no_grad()
+    def top_word_indices(self, topk: int = 10, matrix: str = "beta") -> torch.Tensor:
+        """[K, topk] vocabulary indices of every topic's top words, on the device.
+        ``matrix``: "beta" -- ``best_components`` / ``model.beta`` (what :meth:`get_topics`
+        ranks); "decoder" -- :meth:`topic_word_matrix_tensor` (the same for ProdLDA; for
+        NeuralLDA the softmax_V(BN_K(beta)) the decoder multiplies by)."""
+        if matrix not in ("beta", "decoder"):
+            raise ValueError("matrix must be 'beta' or 'decoder'")
+        if not 0 < int(topk) <= self.input_size:
+            raise ValueError("topk must be in 1 .. input size")
+        if matrix == "beta":
+            comps = self.best_components if self.best_components is not None else self.model.beta
+            comps = comps.detach()
+        else:
+            comps = self.topic_word_matrix_tensor()
+        return torch.topk(comps, int(topk), dim=1).indices
+
+    def _coherence_result(self, topics: torch.Tensor, words: torch.Tensor, counts, n_docs: int,
+                          engine: str, topk: int, per_topic: bool) -> dict:
+        from ..eval.metrics import npmi_from_counts, topic_diversity
+        rows = topics.cpu().tolist()
+        scores = npmi_from_counts(rows, words, counts, n_docs, per_topic=True)
+        return {"npmi": scores if per_topic else float(np.mean(scores)), "per_topic": scores,
+                "diversity": topic_diversity(rows, topk), "topics": topics.cpu().numpy(),
+                "n_docs": int(n_docs), "engine": engine}
+
+    def coherence(self, dataset=None, topk: int = 10, matrix: str = "beta",
+                  per_topic: bool = False) -> dict:
+        """NPMI topic coherence of the model's top-``topk`` words on ``dataset`` (default:
+        the training data), from exact integer document co-occurrence counts taken on the
+        device CSR (eval/metrics.py ``cooccurrence_counts``: csrc/cooc.hip on the GPU, a
+        sparse host product elsewhere) -- no dense [D, W] matrix on either side.
+
+        ``npmi``: the mean over topics (the per-topic list with ``per_topic=True``);
+        ``per_topic``: every topic's value; ``diversity``: ``topic_diversity`` of the same
+        words; ``topics``: the [K, topk] word indices; ``n_docs``; ``engine``: "fused" or
+        "exact".  ``matrix``: see :meth:`top_word_indices`."""
+        from ..eval.metrics import _cooccurrence
+        dataset = self.train_data if dataset is None else dataset
+        if dataset is None:
+            raise ValueError("no dataset given and the model has no training data")
+        data = self.device_data(dataset)
+        topics = self.top_word_indices(topk, matrix)
+        words = torch.unique(topics)
+        counts, engine = _cooccurrence(data, words, None, None)
+        return self._coherence_result(topics, words, counts, int(data.n_docs), engine, topk,
+                                      per_topic)
+
     def _idx2token(self):
         td = self.train_data
         if td is not None and getattr(td, "idx2token", None) is not None:

@@ -174,6 +174,13 @@ class GfkScore(C.Structure):
                 ("grid", C.c_int32), ("doc0", C.c_int32)]
 
 
+class GfkCooc(C.Structure):
+    """word co-occurrence counting launch (csrc/cooc.hip)."""
+    _fields_ = [("indptr", P), ("indices", P), ("values", P), ("slot", P), ("bits", P),
+                ("counts", P), ("n_docs", C.c_int64), ("bits_words", C.c_int64),
+                ("W", C.c_int32), ("V", C.c_int32)]
+
+
 FOLD_W, FOLD_V = 8, 16
 
 
@@ -244,6 +251,13 @@ def declare(lib: C.CDLL) -> None:
     lib.gfk_doc_score_smem.restype = C.c_size_t
     lib.gfk_score_vranges.argtypes = [C.POINTER(GfkModel)]
     lib.gfk_score_vranges.restype = C.c_int
+    lib.gfk_cooc_struct_size.restype = C.c_size_t
+    if lib.gfk_cooc_struct_size() != C.sizeof(GfkCooc):
+        raise RuntimeError("GfkCooc ABI mismatch")
+    lib.gfk_cooc.argtypes = [C.POINTER(GfkCooc), C.c_void_p]
+    lib.gfk_cooc.restype = C.c_int
+    lib.gfk_cooc_max_words.argtypes = []
+    lib.gfk_cooc_max_words.restype = C.c_int
     if hasattr(lib, "gfk_fold_struct_size"):
         lib.gfk_fold_struct_size.restype = C.c_size_t
         lib.gfk_fold_client_struct_size.restype = C.c_size_t
