@@ -207,6 +207,17 @@ constexpr int GFK_LB = 524288;
 // runs as an extra workgroup of row_bwd instead (its inputs -- mu, log sigma^2, KL, RL --
 // are final before row_bwd): M clients' post_bwd is M bmax / 2 workgroups, one round
 constexpr int GFK_POST_ROWS2 = 1048576;
+// stage_flags bit 21 (GFK_POST_JOINT, with bit 20): the workgroup's rows go through each
+// phase of post_bwd's own-row section together (one staging round, one barrier per phase,
+// every weight read from LDS serving all rows) instead of one row after the other; per row
+// the arithmetic is the serial shape's, operation for operation.  Bit 22 (GFK_POST_ROWS4,
+// with bits 20 and 21): four rows per workgroup instead of two
+constexpr int GFK_POST_JOINT = 2097152;
+constexpr int GFK_POST_ROWS4 = 4194304;
+// rows whose own-row vectors post_bwd keeps in LDS at once (1: the serial shapes)
+__host__ __device__ __forceinline__ int gfk_post_joint_rows(int stage_flags) {
+  return !(stage_flags & GFK_POST_JOINT) ? 1 : (stage_flags & GFK_POST_ROWS4) ? 4 : 2;
+}
 constexpr int GFK_BMAX_LIMIT = 512;
 // H[n_hidden - 1] without a runtime index into the descriptor (a batched kernel's copy of it
 // is promoted to registers only when every access has a constant offset)

@@ -646,14 +646,18 @@ __global__ void __launch_bounds__(PT) gfk_row_bwd_k(GfkArgT<GB> ga) {
 // ---------------------------------------------------------------------------
 // LDS plan (floats): dmu, dls, mu, ls [B][K] + s1..s4 [2K] + own-row vectors
 // (dmr|dlr [2K], dz ping-pong [2][hmax], z rows, mask) + staged weights.
+// The own-row vectors (dr, v0, v1, zrow, mask) hold nr rows, row-major: nr = 1 for the
+// serial shapes, the workgroup's R rows for the joint ones (gfk_post_joint_rows); zs = the
+// floats of one row's z rows (all layers).
 struct PostLds {
-  int dmu, dls, mu, ls, sums, pm, dr, v0, v1, zrow, mask, red, red2, w, total;
+  int dmu, dls, mu, ls, sums, pm, dr, v0, v1, zrow, mask, red, red2, w, total, zs;
 };
 
 __host__ __device__ inline PostLds post_lds(const GfkModel& m) {
   PostLds L;
   const int B = m.bmax, K = m.K, hm = pad4(post_hmax(m));
   const int mat = batch_in_lds(m) ? B * post_lds_ld(K) : 0;
+  const int nr = gfk_post_joint_rows(m.stage_flags);
   int o = 0;
   L.dmu = o; o += mat;
   L.dls = o; o += mat;
@@ -661,14 +665,17 @@ __host__ __device__ inline PostLds post_lds(const GfkModel& m) {
   L.ls = o; o += mat;
   L.sums = o; o += 4 * pad4(2 * K);
   L.pm = o; o += pad4(K);
-  L.dr = o; o += 2 * pad4(K);
-  L.v0 = o; o += hm;
-  L.v1 = o; o += hm;
+  L.dr = o; o += nr * 2 * pad4(K);
+  L.v0 = o; o += nr * hm;
+  L.v1 = o; o += nr * hm;
   L.zrow = o;
+  int zs = 0;
 #pragma unroll
   for (int l = 0; l < GFK_MAX_LAYERS; ++l)
-    if (l < m.n_hidden) o += pad4(m.H[l]);
-  L.mask = o; o += pad4(gfk_hlast(m));
+    if (l < m.n_hidden) zs += pad4(m.H[l]);
+  L.zs = zs;
+  o += nr * zs;
+  L.mask = o; o += nr * pad4(gfk_hlast(m));
   L.red = o; o += FT / 64;                // block_sum_wave0 scratch, one float per wave
   L.red2 = o; o += 2 * FT;                // column-reduction scratch [2][FT]
   L.w = o;
@@ -682,39 +689,78 @@ extern "C" size_t gfk_post_bwd_smem(const GfkModel* m) { return sizeof(float) * 
 // out[j] = sum_k term(k, j) for j < n_out: LPO lanes per output split k (DPP quad /
 // row reduction).  LPO = 4 covers 64 outputs per pass of the 256-thread workgroup,
 // so the usual hidden widths take one pass instead of four.
-template <int LPO, class Term, class Epi>
+// NR rows at once: a = term(a, k, j, r, tail) adds term k of row r to the chain a (tail: the
+// odd last term, outside the two-chain loop), epi(j, acc, r) for r < NR.  A lane carries one
+// pair of chains per row and walks k once for all of them (a weight read by term serves
+// every row); each row's sum is the one-row sequence of operations, whatever NR.
+template <int LPO, int NR, class Term, class Epi>
 __device__ __forceinline__ void gemv_lanes(int n_out, int n_in, int tid, Term term, Epi epi) {
   const int s = tid & (LPO - 1);
   for (int j0 = 0; j0 < n_out; j0 += FT / LPO) {
     const int j = j0 + tid / LPO;
-    float acc = 0.f;
+    float acc[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) acc[r] = 0.f;
     if (j < n_out) {
-      float a2 = 0.f;                  // two chains, unrolled: LDS reads of 4 k in flight
+      float a2[NR];                    // two chains, unrolled: LDS reads of 4 k in flight
+#pragma unroll
+      for (int r = 0; r < NR; ++r) a2[r] = 0.f;
       int k = s;
 #pragma unroll 2
       for (; k + LPO < n_in; k += 2 * LPO) {
-        acc += term(k, j);
-        a2 += term(k + LPO, j);
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+          acc[r] = term(acc[r], k, j, r, false);
+          a2[r] = term(a2[r], k + LPO, j, r, false);
+        }
       }
-      if (k < n_in) acc += term(k, j);
-      acc += a2;
+      if (k < n_in) {
+#pragma unroll
+        for (int r = 0; r < NR; ++r) acc[r] = term(acc[r], k, j, r, true);
+      }
+#pragma unroll
+      for (int r = 0; r < NR; ++r) acc[r] += a2[r];
     }
-    acc = LPO == 4 ? quad_sum(acc) : row16_sum(acc);
-    if (s == 0 && j < n_out) epi(j, acc);
+#pragma unroll
+    for (int r = 0; r < NR; ++r) acc[r] = LPO == 4 ? quad_sum(acc[r]) : row16_sum(acc[r]);
+    if (s == 0 && j < n_out) {
+#pragma unroll
+      for (int r = 0; r < NR; ++r) epi(j, acc[r], r);
+    }
   }
 }
 
-template <class Term, class Epi>
+template <int NR, class Term, class Epi>
 __device__ __forceinline__ void gemv_cols(int n_out, int n_in, int tid, Term term, Epi epi) {
-  if (n_out * 16 <= FT) gemv_lanes<16>(n_out, n_in, tid, term, epi);
-  else gemv_lanes<4>(n_out, n_in, tid, term, epi);
+  if (n_out * 16 <= FT) gemv_lanes<16, NR>(n_out, n_in, tid, term, epi);
+  else gemv_lanes<4, NR>(n_out, n_in, tid, term, epi);
 }
 
-// out[j] = sum_k x[k] W[k * ldw + j] for j < n_out (column of a row-major W).
-template <class Epi>
-__device__ __forceinline__ void colvec_gemv(const float* W, int ldw, const float* x, int n_out, int n_in,
-                                            int tid, Epi epi) {
-  gemv_cols(n_out, n_in, tid, [&](int k, int j) { return x[k] * W[k * ldw + j]; }, epi);
+// out[r][j] = sum_k x[r * xs + k] W[k * ldw + j] for j < n_out (column of a row-major W),
+// r < NR rows of x.  NR > 1 (the joint rows) spells out the fused multiply-add the one-row
+// instances compile to (see the unfused operations below).
+template <int NR, class Epi>
+__device__ __forceinline__ void colvec_gemv(const float* W, int ldw, const float* x, int xs, int n_out,
+                                            int n_in, int tid, Epi epi) {
+  gemv_cols<NR>(n_out, n_in, tid, [&](float a, int k, int j, int r, bool) {
+    if constexpr (NR > 1) return __builtin_fmaf(x[r * xs + k], W[k * ldw + j], a);
+    else return a + x[k] * W[k * ldw + j];
+  }, epi);
+}
+
+// fp32 operations the compiler may not fuse with a neighbour.  The joint rows of post_bwd
+// must round exactly like the serial two-row instances (their bitwise reference), whose
+// fusion the compiler chose per expression: BN backward as two fma's around one product,
+// the heads' term as fma(dmr, W_mu, dlr * W_s) inside the two-chain loop but as the sum of
+// two rounded products for the odd last term (packed there), the hidden layers' all fma.
+// The joint section writes those choices out with these and __builtin_fmaf.
+__device__ __forceinline__ float mul_nf(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float add_nf(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
 }
 
 // Column sums over the batch for the BN backward of the heads: s1[c2] = sum_b dy,
@@ -797,9 +843,14 @@ __device__ __forceinline__ void post_prior_sums(int K, int nb, const float* mu, 
 // R rows per workgroup (stage_flags GFK_POST_ROWS2, batched launches: R = 2): the batch
 // matrices, weights and column sums are staged / computed once for both rows, whose own-row
 // sections run one after the other -- M clients' bmax / 2 workgroups fill one round of the
-// CUs (one 16-wave workgroup per CU) where bmax + 1 ran in three
-template <bool InLds, bool Staged, bool GB = false, bool PS = false, int R = 1>
+// CUs (one 16-wave workgroup per CU) where bmax + 1 ran in three.
+// J (stage_flags GFK_POST_JOINT, R = 2 or 4): the R rows' z rows and masks are all staged in
+// the first round and the rows go through BN backward, heads and hidden layers together --
+// one barrier per phase, each lane carrying R accumulator pairs (gemv_lanes).  Rows past nb
+// compute on a clamped row and store nothing.
+template <bool InLds, bool Staged, bool GB = false, bool PS = false, int R = 1, bool J = false>
 __global__ void __launch_bounds__(FT) gfk_post_bwd_k(GfkArgT<GB> ga) {
+  static_assert(!J || (GB && !PS && (R == 2 || R == 4)), "joint rows: batched launches, R = 2 / 4");
   const GfkModel& m = gfk_model_ref(ga);
   extern __shared__ __attribute__((aligned(16))) float smem[];
   int K = m.K, B = m.bmax, nh = m.n_hidden, sflags = m.stage_flags;
@@ -824,7 +875,21 @@ __global__ void __launch_bounds__(FT) gfk_post_bwd_k(GfkArgT<GB> ga) {
     glds_rows(smem + L.mu, mu_g, B, K, LD, tid, FT);
     glds_rows(smem + L.ls, ls_g, B, K, LD, tid, FT);
   }
-  if (!extra) {                         // own row (the extra workgroup has none)
+  if constexpr (J) {                    // every row of the workgroup (past bmax: the last row)
+#pragma unroll
+    for (int rr = 0; rr < R; ++rr) {
+      const int rc = min(r0 + rr, B - 1);
+      int o = L.zrow + rr * L.zs;
+#pragma unroll
+      for (int l = 0; l < GFK_MAX_LAYERS; ++l) {
+        if (l < nh) {
+          glds_copy(smem + o, m.ws_z[l] + (size_t)rc * m.H[l], m.H[l], tid, FT);
+          o += pad4(m.H[l]);
+        }
+      }
+      glds_copy(smem + L.mask + rr * pad4(Hl), m.ws_mask_h + (size_t)rc * Hl, Hl, tid, FT);
+    }
+  } else if (!extra) {                  // own row (the extra workgroup has none)
     int o = L.zrow;
 #pragma unroll
     for (int l = 0; l < GFK_MAX_LAYERS; ++l) {
@@ -959,6 +1024,90 @@ __global__ void __launch_bounds__(FT) gfk_post_bwd_k(GfkArgT<GB> ga) {
   GFK_STAMP(m, 12);
   GFK_STAMP(m, 14);
 
+  if constexpr (J) {
+    // ---- the R rows together; row r's vectors at r times the row strides below ----
+    const int DS = 2 * pad4(K), VS = pad4(post_hmax(m)), MS = pad4(Hl), ZS = L.zs;
+    // ---- BN backward -> d mu_raw | d ls_raw ----
+    float* dr = smem + L.dr;            // [R][dmr | dlr]
+#pragma unroll
+    for (int q = 0; q < CQ; ++q) {
+      const int c2 = tid + q * FT;
+      if (c2 < 2 * K) {
+        const int k = c2 < K ? c2 : c2 - K;
+        const float* dy = c2 < K ? dmu : dls;
+        const float* xh = c2 < K ? mu : ls;
+        float* out = c2 < K ? m.ws_dmr : m.ws_dlr;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          const int rc = min(r0 + r, B - 1);
+          // rs * (dy - S1 / nb - xh S2 / nb), fused as the serial rows' (mul_nf above)
+          const float t = __builtin_fmaf(-S[c2], inv_nb, dy[rc * LD + k]);
+          const float u = mul_nf(xh[rc * LD + k], S[P2 + c2]);
+          const float v = mul_nf(rs[q], __builtin_fmaf(-u, inv_nb, t));
+          dr[r * DS + c2] = v;
+          if (r0 + r < nb) out[(r0 + r) * K + k] = v;
+        }
+      }
+    }
+    lds_barrier();
+    GFK_STAMP(m, 15);
+
+    // ---- heads backward ----
+    const float* wst = smem + L.w;
+    const float* Wmu = staged ? wst : m.w_mu;
+    const float* Ws = staged ? wst + pad4(K * Hl) : m.w_s;
+    float* v0 = smem + L.v0;
+    float* v1 = smem + L.v1;
+    const float* zrow = smem + L.zrow;
+    int zoff_last = 0;
+#pragma unroll
+    for (int l = 0; l + 1 < GFK_MAX_LAYERS; ++l)
+      if (l + 1 < nh) zoff_last += pad4(m.H[l]);
+    {
+      const float* mask = smem + L.mask;
+      const float* zl = zrow + zoff_last;
+      float* dzo = m.ws_dz[nh - 1] + (size_t)r0 * Hl;
+      gemv_cols<R>(Hl, K, tid,
+                   [&](float a, int k, int j, int r, bool tail) {
+                     const float dm = dr[r * DS + k], dl = dr[r * DS + K + k];
+                     const float wm = Wmu[k * Hl + j], ws = Ws[k * Hl + j];
+                     const float t = tail ? add_nf(mul_nf(dm, wm), mul_nf(dl, ws))
+                                          : __builtin_fmaf(dm, wm, mul_nf(dl, ws));
+                     return add_nf(a, t);
+                   },
+                   [&](int j, float acc, int r) {
+                     const float g = mul_nf(mul_nf(acc, mask[r * MS + j]), act_d(m.act, zl[r * ZS + j]));
+                     v0[r * VS + j] = g;
+                     if (r0 + r < nb) dzo[r * Hl + j] = g;
+                   });
+    }
+    lds_barrier();
+    GFK_STAMP(m, 29);
+
+    // ---- hidden layers, last to first ----
+    float* din = v0;
+    float* dout = v1;
+    const float* wl_base = wst + 2 * pad4(K * Hl);
+#pragma unroll
+    for (int l = GFK_MAX_LAYERS - 2; l >= 0; --l) {
+      if (l + 1 >= nh) continue;
+      const int Hi = m.H[l], Ho = m.H[l + 1];
+      int woff = 0, zoff = 0;
+#pragma unroll
+      for (int ll = 0; ll + 1 < GFK_MAX_LAYERS; ++ll)
+        if (ll < l) { woff += pad4(m.H[ll + 1] * m.H[ll]); zoff += pad4(m.H[ll]); }
+      const float* W = staged ? wl_base + woff : m.w_h[l];
+      const float* zl = zrow + zoff;
+      float* dzo = m.ws_dz[l] + (size_t)r0 * Hi;
+      colvec_gemv<R>(W, Hi, din, VS, Hi, Ho, tid, [&](int i, float acc, int r) {
+        const float g = mul_nf(acc, act_d(m.act, zl[r * ZS + i]));
+        dout[r * VS + i] = g;
+        if (r0 + r < nb) dzo[r * Hi + i] = g;
+      });
+      lds_barrier();
+      float* t = din; din = dout; dout = t;
+    }
+  } else {
 #pragma unroll 1
   for (int rr = 0; rr < R; ++rr) {
   row = r0 + rr;
@@ -1009,13 +1158,15 @@ __global__ void __launch_bounds__(FT) gfk_post_bwd_k(GfkArgT<GB> ga) {
     const float* mask = smem + L.mask;
     const float* zl = zrow + zoff_last;
     float* dzo = m.ws_dz[nh - 1] + (size_t)row * Hl;
-    gemv_cols(Hl, K, tid,
-              [&](int k, int j) { return dr[k] * Wmu[k * Hl + j] + dr[K + k] * Ws[k * Hl + j]; },
-              [&](int j, float acc) {
-                const float g = acc * mask[j] * act_d(m.act, zl[j]);
-                v0[j] = g;
-                dzo[j] = g;
-              });
+    gemv_cols<1>(Hl, K, tid,
+                 [&](float a, int k, int j, int, bool) {
+                   return a + (dr[k] * Wmu[k * Hl + j] + dr[K + k] * Ws[k * Hl + j]);
+                 },
+                 [&](int j, float acc, int) {
+                   const float g = acc * mask[j] * act_d(m.act, zl[j]);
+                   v0[j] = g;
+                   dzo[j] = g;
+                 });
   }
   lds_barrier();
   GFK_STAMP(m, 29);
@@ -1035,7 +1186,7 @@ __global__ void __launch_bounds__(FT) gfk_post_bwd_k(GfkArgT<GB> ga) {
     const float* W = staged ? wl_base + woff : m.w_h[l];
     const float* zl = zrow + zoff;
     float* dzo = m.ws_dz[l] + (size_t)row * Hi;
-    colvec_gemv(W, Hi, din, Hi, Ho, tid, [&](int i, float acc) {
+    colvec_gemv<1>(W, Hi, din, 0, Hi, Ho, tid, [&](int i, float acc, int) {
       const float g = acc * act_d(m.act, zl[i]);
       dout[i] = g;
       dzo[i] = g;
@@ -1044,6 +1195,7 @@ __global__ void __launch_bounds__(FT) gfk_post_bwd_k(GfkArgT<GB> ga) {
     float* t = din; din = dout; dout = t;
   }
   }                                     // (rows of the workgroup)
+  }                                     // (serial rows)
   GFK_STAMP(m, 13);
 }
 
@@ -1231,8 +1383,28 @@ extern "C" int gfk_launch_post_bwd(const GfkModel* m, hipStream_t s) {
   const dim3 gb(m->bmax + (moved ? 0 : 1)), tb(FT);   // + the prior / loss / step workgroup
   const size_t sb = gfk_post_bwd_smem(m);
   const bool st = m->stage_flags & 1;
+  const bool joint = m->stage_flags & GFK_POST_JOINT, rows4 = m->stage_flags & GFK_POST_ROWS4;
+  if ((joint && !moved) || (rows4 && !joint)) return -1;
+  if (joint) {
+    // R rows per workgroup, through each phase together (batched launches)
+    const int R = rows4 ? 4 : 2;
+    const dim3 gj = gfk_grid(dim3((m->bmax + R - 1) / R), m);
+    const GfkArgT<true> a{gfk_dev(m)};
+    const int inst = (batch_in_lds(*m) ? 4 : 0) | (st ? 2 : 0) | (rows4 ? 1 : 0);
+    switch (inst) {
+      case 7: hipLaunchKernelGGL((gfk_post_bwd_k<true, true, true, false, 4, true>), gj, tb, sb, s, a); break;
+      case 6: hipLaunchKernelGGL((gfk_post_bwd_k<true, true, true, false, 2, true>), gj, tb, sb, s, a); break;
+      case 5: hipLaunchKernelGGL((gfk_post_bwd_k<true, false, true, false, 4, true>), gj, tb, sb, s, a); break;
+      case 4: hipLaunchKernelGGL((gfk_post_bwd_k<true, false, true, false, 2, true>), gj, tb, sb, s, a); break;
+      case 3: hipLaunchKernelGGL((gfk_post_bwd_k<false, true, true, false, 4, true>), gj, tb, sb, s, a); break;
+      case 2: hipLaunchKernelGGL((gfk_post_bwd_k<false, true, true, false, 2, true>), gj, tb, sb, s, a); break;
+      case 1: hipLaunchKernelGGL((gfk_post_bwd_k<false, false, true, false, 4, true>), gj, tb, sb, s, a); break;
+      default: hipLaunchKernelGGL((gfk_post_bwd_k<false, false, true, false, 2, true>), gj, tb, sb, s, a); break;
+    }
+    return (int)hipGetLastError();
+  }
   if (moved) {
-    // two rows per workgroup (batched launches)
+    // two rows per workgroup, one after the other (batched launches)
     const dim3 g2((m->bmax + 1) / 2 + (moved ? 0 : 1));
     const GfkArgT<true> a{gfk_dev(m)};
     if (batch_in_lds(*m)) {
@@ -1287,7 +1459,11 @@ extern "C" int gfk_post_set_smem(size_t bytes) {
                       (const void*)gfk_row_bwd_k<8>, (const void*)gfk_post_bwd_k<false, true, false, true>,
                       (const void*)gfk_post_bwd_k<false, false, false, true>,
                       (const void*)gfk_post_bwd_k<true, true, true, false, 2>, (const void*)gfk_post_bwd_k<true, false, true, false, 2>,
-                      (const void*)gfk_post_bwd_k<false, true, true, false, 2>, (const void*)gfk_post_bwd_k<false, false, true, false, 2>};
+                      (const void*)gfk_post_bwd_k<false, true, true, false, 2>, (const void*)gfk_post_bwd_k<false, false, true, false, 2>,
+                      (const void*)gfk_post_bwd_k<true, true, true, false, 2, true>, (const void*)gfk_post_bwd_k<true, false, true, false, 2, true>,
+                      (const void*)gfk_post_bwd_k<false, true, true, false, 2, true>, (const void*)gfk_post_bwd_k<false, false, true, false, 2, true>,
+                      (const void*)gfk_post_bwd_k<true, true, true, false, 4, true>, (const void*)gfk_post_bwd_k<true, false, true, false, 4, true>,
+                      (const void*)gfk_post_bwd_k<false, true, true, false, 4, true>, (const void*)gfk_post_bwd_k<false, false, true, false, 4, true>};
   for (const void* k : ks) {
     hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e != hipSuccess) return (int)e;

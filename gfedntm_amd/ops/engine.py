@@ -63,12 +63,33 @@ STAGE_CTX_BWDPP = 4096            # bit 12: CombinedTM backward, persistent pipe
 STAGE_CTX_RS = 32768              # bit 15: CombinedTM forward, Wa register-streamed (csrc/ctx.hip)
 STAGE_FWD_POSTFOLD = 65536        # bit 16: the strip forward computes post_fwd (csrc/prodlda.hip FP)
 STAGE_LB = 524288                 # bit 19: the large-batch plan (bmax 256 / 512, csrc/gfk_common.h)
-STAGE_POST_ROWS2 = 1048576        # bit 20: batched post_bwd, two rows per workgroup; its batch-level
-                                  #         workgroup in row_bwd (csrc/posterior.hip)
+STAGE_POST_ROWS2 = abi.POST_ROWS2  # bit 20: batched post_bwd, two rows per workgroup; its batch-level
+                                   #         workgroup in row_bwd (csrc/posterior.hip)
+STAGE_POST_JOINT = abi.POST_JOINT  # bit 21: ... the rows through each phase together (with bit 20)
+STAGE_POST_ROWS4 = abi.POST_ROWS4  # bit 22: ... four rows per workgroup (with bits 20 and 21)
+# the shape GFEDNTM_POST_ROWS=auto takes where bit 20 applies (a key of abi.POST_ROWS_SHAPES):
+# the headline's interleaved A/B, 8 clients K = 50 (profiles/r7/ab_post_rows.txt): serial2
+# 0.1176 ms per round, two joint rows 0.1159, four 0.1193
+POST_ROWS_AUTO = "2"
 # (removed in round 6, measured not faster: bits 3 / 8 the strip forward's 8-wave whole-block
 # prefetch vs its ring (now the only variant), bit 6 the plain rolling prefetch, 7 the split W_in update, 10 the sparse tile's register second moment
 # as a knob, 11 / 13 the LDS-DMA balanced CombinedTM forwards, 14 the persistent Wc update,
 # 17 the moved batch-level workgroup on its own, 18 the one-range backward walking tiles)
+
+
+def post_rows_flags(n_clients: int, bmax: int, cus: int, knob: str = "auto") -> int:
+    """stage_flags bits of a batched launch's post_bwd shape (GFEDNTM_POST_ROWS).
+
+    ``auto``: where M clients' bmax + 1 one-row workgroups exceed one round of the CUs, the
+    shape POST_ROWS_AUTO; else none (the one-row shape).  ``serial2`` / ``2`` / ``4`` force
+    that shape on every launch of M > 1 clients, whatever the CU count."""
+    if n_clients < 2:
+        return 0
+    if knob == "auto":
+        return abi.POST_ROWS_SHAPES[POST_ROWS_AUTO] if n_clients * (bmax + 1) > cus else 0
+    if knob not in abi.POST_ROWS_SHAPES:
+        raise ValueError(f"GFEDNTM_POST_ROWS={knob!r}: expected auto, serial2, 2 or 4")
+    return abi.POST_ROWS_SHAPES[knob]
 
 
 def engine_bmax(tm) -> int:
@@ -1696,8 +1717,22 @@ class BatchedSteps:
             # (M (bmax + 1) <= CUs: the one-row shape).  Round 6 removed the opt-in variants
             # measured slower: the matrices read from L2, and the persistent one-range
             # backward walking several tiles (profiles/r5/ab_batch.txt).
-            if M > 1 and M * (mm.bmax + 1) > self._cu:
-                mm.stage_flags |= STAGE_POST_ROWS2
+            # GFEDNTM_POST_ROWS = auto | serial2 | 2 | 4: the rows of a workgroup one after the
+            # other (serial2) or through each phase together (2 / 4 rows, bits 21 / 22; the
+            # own-row vectors of all rows in LDS: gfk_setup raises the kernels' limit)
+            knob = os.environ.get("GFEDNTM_POST_ROWS", "auto")
+            post = post_rows_flags(M, mm.bmax, self._cu, knob)
+            if post & STAGE_POST_JOINT:
+                mm.stage_flags |= post
+                if e.lib.gfk_smem_required(C.byref(mm), 4) > LDS_LIMIT:
+                    if knob != "auto":
+                        raise RuntimeError(f"GFEDNTM_POST_ROWS={knob}: the rows' vectors do not fit the LDS")
+                    mm.stage_flags &= ~(STAGE_POST_JOINT | STAGE_POST_ROWS4)
+                else:
+                    rc = e.lib.gfk_setup(C.byref(mm))
+                    if rc:
+                        raise RuntimeError(f"gfk_setup failed ({rc})")
+            mm.stage_flags |= post & STAGE_POST_ROWS2
             # CombinedTM: M clients' vocabulary tiles in one launch fill the CUs the way one
             # client's do at a large vocabulary, so the batched launch takes that plan -- the
             # forward with all batch rows per tile (each Wa block staged once) and the

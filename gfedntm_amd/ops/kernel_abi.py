@@ -17,6 +17,16 @@ ACT_CODES = {"softplus": 0, "relu": 1, "sigmoid": 2, "tanh": 3, "leakyrelu": 4, 
 KIND_PRODLDA, KIND_LDA = 0, 1
 IN_BOW, IN_COMBINED, IN_CONTEXTUAL = 0, 1, 2
 
+# stage_flags bits of the batched post_bwd (csrc/gfk_common.h GFK_POST_ROWS2 / GFK_POST_JOINT /
+# GFK_POST_ROWS4): several rows per workgroup with the batch-level workgroup in row_bwd; the
+# rows through each phase together; four rows instead of two (needs both others)
+POST_ROWS2 = 1 << 20
+POST_JOINT = 1 << 21
+POST_ROWS4 = 1 << 22
+# GFEDNTM_POST_ROWS value -> those bits (ops/engine.py post_rows_flags)
+POST_ROWS_SHAPES = {"serial2": POST_ROWS2, "2": POST_ROWS2 | POST_JOINT,
+                    "4": POST_ROWS2 | POST_JOINT | POST_ROWS4}
+
 # phase ids (csrc/step.cpp GfkPhase)
 PH_BATCH_DOCS = 0
 PH_ENC_FWD = 1
