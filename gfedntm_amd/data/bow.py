@@ -106,6 +106,37 @@ class DeviceCSR:
         self.labels = None if labels is None else torch.from_numpy(
             np.ascontiguousarray(labels, dtype=np.float32)).to(self.device)
 
+    @classmethod
+    def from_tensors(cls, indptr: torch.Tensor, indices: torch.Tensor, values: torch.Tensor,
+                     shape, contextual: Optional[torch.Tensor] = None,
+                     labels: Optional[torch.Tensor] = None) -> "DeviceCSR":
+        """A DeviceCSR over tensors that already live on one device (a CSR a kernel wrote):
+        ``indptr`` [D+1], ``indices`` [nnz] sorted per row, ``values`` [nnz].  Nothing is
+        uploaded; ``row_len_max`` costs one reduction.  ``contextual`` / ``labels`` are
+        shared with the caller, not copied."""
+        n_docs, vocab_size = int(shape[0]), int(shape[1])
+        if indptr.dim() != 1 or indptr.numel() != n_docs + 1:
+            raise ValueError(f"indptr must hold {n_docs + 1} row pointers")
+        if indices.dim() != 1 or indices.shape != values.shape:
+            raise ValueError("indices and values must be 1-d and of one length")
+        if indices.numel() >= 2**31:
+            raise ValueError("shard too large for int32 CSR offsets; split it")
+        dev = indptr.device
+        for name, t in (("indices", indices), ("values", values), ("contextual", contextual),
+                        ("labels", labels)):
+            if t is not None and t.device != dev:
+                raise ValueError(f"{name} is on {t.device}, indptr on {dev}")
+        self = cls.__new__(cls)
+        self.n_docs, self.vocab_size = n_docs, vocab_size
+        self.device = dev
+        self.indptr = indptr.to(torch.int32).contiguous()
+        self.indices = indices.to(torch.int32).contiguous()
+        self.values = values.to(torch.float32).contiguous()
+        self.row_len_max = int((self.indptr[1:] - self.indptr[:-1]).max().item()) if n_docs else 0
+        self.nnz = int(indices.numel())
+        self.contextual, self.labels = contextual, labels
+        return self
+
     def dense_rows(self, doc_ids: torch.Tensor) -> torch.Tensor:
         """Densify a set of rows on device (used by the pure-torch backend)."""
         doc_ids = doc_ids.to(self.device, torch.long)

@@ -84,10 +84,30 @@ def read_corpus(path):
 
 
 def htm_ws_counts(X: sp.csr_matrix, thetas: np.ndarray, betas: np.ndarray, topic: int,
-                  seed: int = 0, device=None, chunk: int = 1 << 20) -> sp.csr_matrix:
+                  seed: int = 0, device=None, chunk: int = 1 << 20,
+                  engine: Optional[str] = None) -> sp.csr_matrix:
     """Tokens of every (d, w) non-zero of ``X`` assigned to ``topic``:
-    Binomial(x_dw, theta_d,topic beta_topic,w / sum_k theta_dk beta_kw)."""
+    Binomial(x_dw, theta_d,topic beta_topic,w / sum_k theta_dk beta_kw).
+
+    ``engine=None``: ``torch.binomial`` draws from the device's generator, in chunks of
+    ``chunk`` non-zeros (they depend on the device and the chunk size).  ``"keyed"``:
+    ``ops/thin.py thin_by_topic`` -- Philox draws keyed by (seed, document, word, token),
+    made by the kernels of csrc/thin.hip when ``device`` is a GPU and by their numpy twin
+    otherwise, so a seed names one corpus whatever the chunking."""
+    if engine not in (None, "keyed"):
+        raise ValueError("engine must be None or 'keyed'")
     X = X.tocsr()
+    if engine == "keyed":
+        from ..data.bow import DeviceCSR
+        from ..ops import thin
+        dev = torch.device(device) if device is not None else torch.device("cpu")
+        if dev.type != "cuda":
+            return thin.thin_by_topic(X, np.asarray(thetas), np.asarray(betas), topic, seed,
+                                      engine="host")
+        kept = thin.thin_by_topic(DeviceCSR(X, dev), np.asarray(thetas), np.asarray(betas), topic,
+                                  seed, engine="fused")
+        return sp.csr_matrix((kept.values.cpu().numpy(), kept.indices.cpu().numpy(),
+                              kept.indptr.cpu().numpy()), shape=X.shape)
     dev = torch.device(device) if device is not None else torch.device("cpu")
     th = torch.as_tensor(np.asarray(thetas, dtype=np.float32), device=dev)
     be = torch.as_tensor(np.asarray(betas, dtype=np.float32), device=dev)
@@ -127,11 +147,14 @@ def _bool(v) -> bool:
 class TMWrapper:
     """Same entry points as the reference TMWrapper (tm_wrapper.py:15-400)."""
 
-    def __init__(self, logger=None, device=None, seed: int = 0):
+    def __init__(self, logger=None, device=None, seed: int = 0, htm_engine: Optional[str] = None):
         self._logger = logger or logging.getLogger("TMWrapper")
         self.device = torch.device(device) if device is not None else torch.device(
             "cuda" if torch.cuda.is_available() else "cpu")
         self.seed = int(seed)
+        if htm_engine not in (None, "keyed"):
+            raise ValueError("htm_engine must be None or 'keyed'")
+        self.htm_engine = htm_engine      # HTM-WS draws: htm_ws_counts(engine=...)
 
     # ------------------------------------------------------------------ config
     def _get_model_config(self, trainer: str, TMparam: dict, hierarchy_level: int,
@@ -304,7 +327,7 @@ class TMWrapper:
             X = vectorize(df["bow_text"].tolist(), {t: i for i, t in enumerate(terms)})
             betas = np.load(tmd / "betas.npy")
             kept = htm_ws_counts(X, thetas, betas, expansion_topic, seed=self.seed,
-                                 device=self.device)
+                                 device=self.device, engine=self.htm_engine)
             texts = np.asarray(counts_to_texts(kept, terms), dtype=object)
             mask = np.diff(kept.indptr) > 0
             sub = df.loc[mask].copy()

@@ -291,10 +291,13 @@ class TopicModelBase:
         raise NotImplementedError
 
     @torch.no_grad()
-    def _score_torch(self, data: DeviceCSR, n_samples: int, seed: int, eps=None):
+    def _score_torch(self, data: DeviceCSR, n_samples: int, seed: int, eps=None,
+                     target: Optional[DeviceCSR] = None):
         """Per-document (KL, RL[, CE]) on the PyTorch modules in eval mode, from the CSR in
         chunks of dense rows (never [D, V]).  ``eps``: explicit normals [n_samples, D, K]
-        instead of torch's generator, so two engines can be compared draw for draw."""
+        instead of torch's generator, so two engines can be compared draw for draw.
+        ``target``: a second CSR of the same documents whose rows the reconstruction term
+        is taken on (document completion); the encoder reads ``data``."""
         from .networks import reconstruction_terms
         n, K, S = int(data.n_docs), self.n_components, int(n_samples)
         model = self.model
@@ -313,6 +316,8 @@ class TopicModelBase:
         for a in range(0, n, chunk):
             ids = torch.arange(a, min(a + chunk, n), device=self.device)
             x, mu, logvar, lab = self._encode_rows(data, ids)
+            if target is not None:
+                x = target.dense_rows(ids)
             kls.append(kl_terms(model.prior_mean, model.prior_variance, mu, torch.exp(logvar),
                                 logvar, K))
             std = torch.exp(0.5 * logvar)
@@ -341,7 +346,8 @@ class TopicModelBase:
         return torch.cat(kls), torch.cat(rls), (torch.cat(ces) if ces else None)
 
     def score(self, dataset, n_samples: int = 1, seed: Optional[int] = None, eps=None,
-              engine: Optional[str] = None) -> dict:
+              engine: Optional[str] = None, completion: Optional[float] = None,
+              split_seed: Optional[int] = None) -> dict:
         """How well the model explains (held-out) documents: per-document ELBO terms, the
         corpus loss and the perplexity.
 
@@ -353,10 +359,25 @@ class TopicModelBase:
         label head; ``perplexity``: exp(sum(KL + RL) / tokens); ``engine``: "fused"
         (csrc/score.hip) or "torch" (the eval-mode modules; ``engine_info`` says why).
         ``eps``: explicit normals [n_samples, D, K] -- PyTorch engine only; ``engine``
-        forces one of the two ("fused" raises where the kernels do not cover the model)."""
+        forces one of the two ("fused" raises where the kernels do not cover the model).
+
+        ``completion=rho`` (0 < rho < 1) scores by document completion: every token is
+        observed with probability rho (``ops/thin.py split``, keyed by ``split_seed`` --
+        default ``seed`` --, document, word and token, so every engine sees the same
+        split); the encoder reads the observed part and ``rl`` is taken on the held-out
+        rest, which makes models whose encoders read different inputs comparable.
+        ``perplexity`` is then exp(sum(RL) / held-out tokens), without the KL, and the
+        result gains ``completion``, ``tokens_observed`` and ``tokens_heldout``."""
         data = self.device_data(dataset)
         if seed is None:
             seed = int(torch.initial_seed()) % (2**31)
+        target = None
+        if completion is not None:
+            completion = float(completion)
+            if not 0.0 < completion < 1.0:
+                raise ValueError("completion must lie strictly between 0 and 1")
+            from ..ops import thin
+            data, target = thin.split(data, completion, seed if split_seed is None else split_seed)
         if engine not in (None, "fused", "torch"):
             raise ValueError("engine must be None, 'fused' or 'torch'")
         if engine == "fused":
@@ -368,10 +389,10 @@ class TopicModelBase:
             engine = "torch" if eps is not None else self._score_engine()[0]
         ce = None
         if engine == "fused":
-            klrl = self.engine.score(data, n_samples, seed=seed).cpu().numpy()
+            klrl = self.engine.score(data, n_samples, seed=seed, target=target).cpu().numpy()
             kl, rl = klrl[:, 0].copy(), klrl[:, 1].copy()
         else:
-            kl, rl, ce = self._score_torch(data, n_samples, seed, eps)
+            kl, rl, ce = self._score_torch(data, n_samples, seed, eps, target=target)
             packed = torch.stack([kl, rl] + ([ce] if ce is not None else []), 1).cpu().numpy()
             kl, rl = packed[:, 0].copy(), packed[:, 1].copy()
             ce = packed[:, 2].copy() if ce is not None else None
@@ -381,18 +402,28 @@ class TopicModelBase:
         if ce is not None:
             B = self.batch_size
             total += float(sum(ce[a:a + B].astype(np.float64).mean() for a in range(0, n, B)))
-        tokens = float(dataset.csr.sum())
-        elbo = float(np.sum(kl.astype(np.float64) + rl.astype(np.float64)))
+        if target is None:
+            tokens = float(dataset.csr.sum())
+            nll = float(np.sum(kl.astype(np.float64) + rl.astype(np.float64)))
+        else:               # predictive: the held-out tokens' reconstruction term alone
+            tokens = float(target.values.sum(dtype=torch.float64).item())
+            nll = float(np.sum(rl.astype(np.float64)))
         out = {"kl": kl, "rl": rl, "loss": total / max(n, 1),
-               "perplexity": float(np.exp(elbo / tokens)) if tokens > 0 else float("nan"),
+               "perplexity": float(np.exp(nll / tokens)) if tokens > 0 else float("nan"),
                "engine": engine}
         if ce is not None:
             out["ce"] = ce
+        if target is not None:
+            out.update(completion=completion, tokens_heldout=int(tokens),
+                       tokens_observed=int(data.values.sum(dtype=torch.float64).item()))
         return out
 
-    def perplexity(self, dataset, n_samples: int = 1, seed: Optional[int] = None) -> float:
-        """exp(sum_d (KL_d + RL_d) / sum_d N_d) -- shorthand for :meth:`score`."""
-        return self.score(dataset, n_samples=n_samples, seed=seed)["perplexity"]
+    def perplexity(self, dataset, n_samples: int = 1, seed: Optional[int] = None,
+                   completion: Optional[float] = None, split_seed: Optional[int] = None) -> float:
+        """exp(sum_d (KL_d + RL_d) / sum_d N_d) -- shorthand for :meth:`score`; with
+        ``completion``, the predictive exp(sum_d RL_d / held-out tokens)."""
+        return self.score(dataset, n_samples=n_samples, seed=seed, completion=completion,
+                          split_seed=split_seed)["perplexity"]
 
     def fit(self, train_dataset, validation_dataset=None, save_dir=None, patience=5, delta=0,
             n_samples=20):

@@ -1360,7 +1360,7 @@ class FusedEngine(EngineBase):
 
     @torch.no_grad()
     def score(self, data: DeviceCSR, n_samples: int = 1, seed: int = 0,
-              chunk: Optional[int] = None) -> torch.Tensor:
+              chunk: Optional[int] = None, target: Optional[DeviceCSR] = None) -> torch.Tensor:
         """Held-out ELBO terms [D, 2] = (KL, RL) of every document of ``data``
         (csrc/score.hip): the eval-mode encoder once per document (gfk_theta_infer, the
         posterior moments), then the eval-mode ProdLDA decoder over ``n_samples`` draws of
@@ -1368,7 +1368,9 @@ class FusedEngine(EngineBase):
         for the same seed; ``n_samples=0`` scores the plug-in theta = softmax(mu).  RL is
         the mean over the draws, KL is exact.  Always fp32.  No dense [rows, V] matrix is
         built and nothing is read back: the result stays on the device.  Draws are keyed by
-        (seed, document index), so neither the chunking nor the grid changes the result."""
+        (seed, document index), so neither the chunking nor the grid changes the result.
+        ``target``: a second CSR of the same documents (document completion, ops/thin.py
+        split): the encoder reads ``data``, the sparse reconstruction term ``target``."""
         score_supports(self.tm, explain=True)
         m, K, n, S = self._m, int(self._m.K), int(data.n_docs), int(n_samples)
         if S < 0:
@@ -1381,6 +1383,9 @@ class FusedEngine(EngineBase):
             chunk = max(64, min(self._infer_chunk(), (1 << 16) // R))
         if int(data.vocab_size) != int(m.V):
             raise ValueError(f"data has {data.vocab_size} columns, the model {int(m.V)}")
+        rec = data if target is None else target
+        if (int(rec.n_docs), int(rec.vocab_size)) != (n, int(m.V)) or rec.device != data.device:
+            raise ValueError("target must hold the same documents and columns as data, on its device")
         f = dict(dtype=torch.float32, device=self.device)
         rows = min(n, chunk) * R
         mom = torch.empty(min(n, chunk), 2 * K, **f)
@@ -1396,8 +1401,8 @@ class FusedEngine(EngineBase):
             d1 = min(n, d0 + chunk)
             self._infer_launch(data, d0, d1, mom.data_ptr(), 1, abi.INFER_MOMENTS, 0.0, seed)
             p = abi.GfkScore()
-            p.indptr = data.indptr.data_ptr() + 4 * d0
-            p.indices, p.values = data.indices.data_ptr(), data.values.data_ptr()
+            p.indptr = rec.indptr.data_ptr() + 4 * d0
+            p.indices, p.values = rec.indices.data_ptr(), rec.values.data_ptr()
             p.moments, p.theta, p.lse_part = mom.data_ptr(), theta.data_ptr(), lse_part.data_ptr()
             p.rl_rows, p.out = rl_rows.data_ptr(), out.data_ptr() + 8 * d0
             p.n_docs, p.n_samples = d1 - d0, S

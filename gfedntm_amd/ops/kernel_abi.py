@@ -191,6 +191,19 @@ class GfkCooc(C.Structure):
                 ("W", C.c_int32), ("V", C.c_int32)]
 
 
+class GfkThin(C.Structure):
+    """token-wise thinning launch (csrc/thin.hip)."""
+    _fields_ = [("indptr", P), ("indices", P), ("values", P), ("theta", P), ("tw", P),
+                ("kept", P), ("p_out", P), ("n_kept", P), ("n_rest", P),
+                ("kept_ptr", P), ("rest_ptr", P), ("kept_idx", P), ("kept_val", P),
+                ("rest_idx", P), ("rest_val", P),
+                ("seed", C.c_uint64), ("rate", C.c_float),
+                ("n_docs", C.c_int32), ("K", C.c_int32), ("V", C.c_int32), ("ld", C.c_int32),
+                ("topic", C.c_int32), ("doc0", C.c_int32), ("pass_", C.c_int32)]
+
+
+THIN_COUNT, THIN_COMPACT = 1, 2
+
 FOLD_W, FOLD_V = 8, 16
 
 
@@ -268,6 +281,13 @@ def declare(lib: C.CDLL) -> None:
     lib.gfk_cooc.restype = C.c_int
     lib.gfk_cooc_max_words.argtypes = []
     lib.gfk_cooc_max_words.restype = C.c_int
+    lib.gfk_thin_struct_size.restype = C.c_size_t
+    if lib.gfk_thin_struct_size() != C.sizeof(GfkThin):
+        raise RuntimeError("GfkThin ABI mismatch")
+    lib.gfk_thin.argtypes = [C.POINTER(GfkThin), C.c_void_p]
+    lib.gfk_thin.restype = C.c_int
+    lib.gfk_thin_max_topics.argtypes = []
+    lib.gfk_thin_max_topics.restype = C.c_int
     if hasattr(lib, "gfk_fold_struct_size"):
         lib.gfk_fold_struct_size.restype = C.c_size_t
         lib.gfk_fold_client_struct_size.restype = C.c_size_t
