@@ -32,6 +32,7 @@
 // (p / m / v of V x C floats), which is what bounds it.
 #define GFK_BATCHED_COPY 1   // batched kernels copy their descriptor (gfk_common.h gfk_model)
 #include "gfk_common.h"
+#include "gfk_launch.h"
 
 using namespace gfk;
 
@@ -1037,27 +1038,6 @@ extern "C" size_t gfk_ctx_smem(const GfkModel* m) {
   return sizeof(float) * (a > b ? a : b);
 }
 
-extern "C" int gfk_ctx_set_smem(size_t bytes) {
-  // the attribute is per function and process-wide: only ever raise it, so an engine
-  // built earlier with a larger footprint keeps launching after a smaller one is set up
-  static size_t cur = 0;
-  if (bytes <= cur) return 0;
-  cur = bytes;
-  const void* ks[] = {(const void*)gfk_ctx_fwd_k<16>, (const void*)gfk_ctx_fwd_k<16, true>, (const void*)gfk_ctx_fwd_k<32>, (const void*)gfk_ctx_fwd_k<32, true>,
-                      (const void*)gfk_ctx_fwd_k<64>, (const void*)gfk_ctx_fwd_k<64, true>, (const void*)gfk_ctx_fwd_k<128>, (const void*)gfk_ctx_fwd_k<128, true>,
-                      (const void*)gfk_ctx_bwd_k<16>, (const void*)gfk_ctx_bwd_k<16, true>, (const void*)gfk_ctx_bwd_k<32>, (const void*)gfk_ctx_bwd_k<32, true>,
-                      (const void*)gfk_ctx_bwd_k<64>, (const void*)gfk_ctx_bwd_k<64, true>, (const void*)gfk_ctx_bwd_k<128>, (const void*)gfk_ctx_bwd_k<128, true>,
-                      (const void*)gfk_ctx_fwd_full_k<false>, (const void*)gfk_ctx_fwd_full_k<true>,
-                      (const void*)gfk_ctx_bwd_pp_k<false>, (const void*)gfk_ctx_bwd_pp_k<true>,
-                      (const void*)gfk_ctx_fwd_rs_k<false>, (const void*)gfk_ctx_fwd_rs_k<true>,
-                      (const void*)gfk_ctx_fwd_rs_k<false, true>, (const void*)gfk_ctx_fwd_rs_k<true, true>};
-  for (const void* k : ks) {
-    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) return (int)e;
-  }
-  return 0;
-}
-
 // Host checks mirror the kernels' assumptions: the backward chunk a multiple of 16
 // and <= 256 (prefetch slots), H0 <= 512, float4-aligned contextual rows / Wa.
 static bool ctx_ok(const GfkModel* m) {
@@ -1068,55 +1048,44 @@ static bool ctx_ok(const GfkModel* m) {
          (int64_t)m->ctx_kb * m->ctx_ckb >= m->C;
 }
 
+// The instance table (csrc/gfk_launch.h): a launcher looks its kernel up by the key it
+// computes from the model, and gfk_ctx_set_smem raises the dynamic-LDS limit of the same
+// rows.  A new instance is one new row.  {kernel, bmax (the tile kernels) | bf16 (rs)}
+enum { CTXK_FWD, CTXK_FWD_FULL, CTXK_FWD_RS, CTXK_BWD, CTXK_BWD_PP };
+#define CTX_ROWS(BM) {{CTXK_FWD, BM}, GFK_PAIR(gfk_ctx_fwd_k, BM)}, {{CTXK_BWD, BM}, GFK_PAIR(gfk_ctx_bwd_k, BM)}
+static const GfkRow kCtx[] = {CTX_ROWS(16), CTX_ROWS(32), CTX_ROWS(64), CTX_ROWS(128),
+                              {{CTXK_FWD_FULL}, {gfk_ctx_fwd_full_k<false>, gfk_ctx_fwd_full_k<true>}},
+                              {{CTXK_FWD_RS, 0}, {gfk_ctx_fwd_rs_k<false, false>, gfk_ctx_fwd_rs_k<true, false>}},
+                              {{CTXK_FWD_RS, 1}, {gfk_ctx_fwd_rs_k<false, true>, gfk_ctx_fwd_rs_k<true, true>}},
+                              {{CTXK_BWD_PP}, {gfk_ctx_bwd_pp_k<false>, gfk_ctx_bwd_pp_k<true>}}};
+#undef CTX_ROWS
+
+extern "C" int gfk_ctx_set_smem(size_t bytes) {
+  static size_t cur = 0;
+  return gfk_lds_raised(cur, bytes) ? gfk_raise_lds(kCtx, bytes) : 0;
+}
+
 extern "C" int gfk_launch_ctx_fwd(const GfkModel* m, hipStream_t s) {
   if (!ctx_ok(m)) return -9;
   // register-streamed forward: at most 2 units per wave (32 per workgroup), 32-bit buffer
   // offsets into Wa and the flat buffer (engine checks), Wa rows 16-byte aligned
   if ((m->stage_flags & CTX_FULL) && (m->stage_flags & CTX_RS) && m->bmax <= 64 && m->H[0] <= 64 &&
       m->ctx_parts > 0 && ((m->V + 15) / 16 + m->ctx_parts - 1) / m->ctx_parts <= 32 &&
-      (int64_t)m->V * m->C * 4 < 0x7FFFFFFFLL) {
-    const dim3 g(m->ctx_parts), t(RS_T);
-    const size_t sm = sizeof(float) * fwd_rs_lds_floats();
-    if (m->mm_bf16)
-      do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_ctx_fwd_rs_k<true, true>), gfk_grid(g, m), t, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_ctx_fwd_rs_k<false, true>), g, t, sm, s, GfkArgT<false>{*m}); } while (0);
-    else
-      do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_ctx_fwd_rs_k<true>), gfk_grid(g, m), t, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_ctx_fwd_rs_k<false>), g, t, sm, s, GfkArgT<false>{*m}); } while (0);
-    return (int)hipGetLastError();
-  }
-  if ((m->stage_flags & CTX_FULL) && m->bmax <= 64) {
-    const dim3 g(m->n_tiles), t(FT);
-    const size_t sm = sizeof(float) * fwd_full_lds_floats(*m);
-    do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_ctx_fwd_full_k<true>), gfk_grid(g, m), t, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_ctx_fwd_full_k<false>), g, t, sm, s, GfkArgT<false>{*m}); } while (0);
-    return (int)hipGetLastError();
-  }
+      (int64_t)m->V * m->C * 4 < 0x7FFFFFFFLL)
+    return gfk_launch(gfk_find(kCtx, CTXK_FWD_RS, m->mm_bf16 ? 1 : 0), m, dim3(m->ctx_parts), dim3(RS_T),
+                      sizeof(float) * fwd_rs_lds_floats(), s);
+  if ((m->stage_flags & CTX_FULL) && m->bmax <= 64)
+    return gfk_launch(gfk_find(kCtx, CTXK_FWD_FULL), m, dim3(m->n_tiles), dim3(FT),
+                      sizeof(float) * fwd_full_lds_floats(*m), s);
   const dim3 g(8 * ((m->n_tiles + 7) / 8) * (m->bmax / 16)), t(FT);
-  const size_t sm = sizeof(float) * fwd_lds_floats(*m);
-  switch (m->bmax) {
-    case 16: do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_ctx_fwd_k<16, true>), gfk_grid(g, m), t, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_ctx_fwd_k<16, false>), g, t, sm, s, GfkArgT<false>{*m}); } while (0); break;
-    case 32: do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_ctx_fwd_k<32, true>), gfk_grid(g, m), t, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_ctx_fwd_k<32, false>), g, t, sm, s, GfkArgT<false>{*m}); } while (0); break;
-    case 64: do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_ctx_fwd_k<64, true>), gfk_grid(g, m), t, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_ctx_fwd_k<64, false>), g, t, sm, s, GfkArgT<false>{*m}); } while (0); break;
-    case 128: do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_ctx_fwd_k<128, true>), gfk_grid(g, m), t, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_ctx_fwd_k<128, false>), g, t, sm, s, GfkArgT<false>{*m}); } while (0); break;
-    default: return -1;
-  }
-  return (int)hipGetLastError();
+  return gfk_launch(gfk_find(kCtx, CTXK_FWD, m->bmax), m, g, t, sizeof(float) * fwd_lds_floats(*m), s);
 }
 
 extern "C" int gfk_launch_ctx_bwd(const GfkModel* m, hipStream_t s) {
   if (!ctx_ok(m)) return -9;
-  if ((m->stage_flags & CTX_BWDPP) && m->bmax <= 64 && m->H[0] <= 64 && m->ctx_bgrid > 0) {
-    const dim3 g(m->ctx_bgrid), t(CT);
-    const size_t sm = sizeof(float) * pp_lds(*m).total;
-    do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_ctx_bwd_pp_k<true>), gfk_grid(g, m), t, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_ctx_bwd_pp_k<false>), g, t, sm, s, GfkArgT<false>{*m}); } while (0);
-    return (int)hipGetLastError();
-  }
+  if ((m->stage_flags & CTX_BWDPP) && m->bmax <= 64 && m->H[0] <= 64 && m->ctx_bgrid > 0)
+    return gfk_launch(gfk_find(kCtx, CTXK_BWD_PP), m, dim3(m->ctx_bgrid), dim3(CT),
+                      sizeof(float) * pp_lds(*m).total, s);
   const dim3 g(m->n_tiles * m->ctx_kb), t(CT);
-  const size_t sm = sizeof(float) * bwd_lds(*m).total;
-  switch (m->bmax) {
-    case 16: do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_ctx_bwd_k<16, true>), gfk_grid(g, m), t, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_ctx_bwd_k<16, false>), g, t, sm, s, GfkArgT<false>{*m}); } while (0); break;
-    case 32: do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_ctx_bwd_k<32, true>), gfk_grid(g, m), t, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_ctx_bwd_k<32, false>), g, t, sm, s, GfkArgT<false>{*m}); } while (0); break;
-    case 64: do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_ctx_bwd_k<64, true>), gfk_grid(g, m), t, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_ctx_bwd_k<64, false>), g, t, sm, s, GfkArgT<false>{*m}); } while (0); break;
-    case 128: do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_ctx_bwd_k<128, true>), gfk_grid(g, m), t, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_ctx_bwd_k<128, false>), g, t, sm, s, GfkArgT<false>{*m}); } while (0); break;
-    default: return -1;
-  }
-  return (int)hipGetLastError();
+  return gfk_launch(gfk_find(kCtx, CTXK_BWD, m->bmax), m, g, t, sizeof(float) * bwd_lds(*m).total, s);
 }

@@ -23,6 +23,7 @@
 // (batched descriptor by reference: with the copy (gfk_common.h gfk_model) the narrow
 // instance ran 14.5 -> 20 us at M = 8, profiles/r5/ab_batched_copy2.txt)
 #include "gfk_common.h"
+#include "gfk_launch.h"
 
 using namespace gfk;
 
@@ -436,43 +437,23 @@ gfk_enc_in_k(GfkArgT<GB> ga) {
   GFK_STAMP(m, 39);
 }
 
+// The instance table (csrc/gfk_launch.h): the launcher looks its kernel up by the key it
+// computes from the model, and gfk_enc_in_set_smem raises the dynamic-LDS limit of the same
+// rows.  A new instance is one new row.  {staged weights, narrow (H0 <= 64)}
+static const GfkRow kEncIn[] = {{{1, 0}, {gfk_enc_in_k<true, false>, gfk_enc_in_k<true, true>}},
+                                {{0, 0}, {gfk_enc_in_k<false, false>, gfk_enc_in_k<false, true>}},
+                                {{1, 1}, {gfk_enc_in_k<true, false, 1>, gfk_enc_in_k<true, true, 1>}},
+                                {{0, 1}, {gfk_enc_in_k<false, false, 1>, gfk_enc_in_k<false, true, 1>}}};
+
 extern "C" int gfk_launch_enc_in(const GfkModel* m, hipStream_t s) {
-  if (m->H[0] <= 64 && (m->stage_flags & 1)) {   // narrow, staged: two workgroups per CU
-    if (m->n_batch > 1)
-      hipLaunchKernelGGL((gfk_enc_in_k<true, true, 1>), gfk_grid(dim3(m->bmax), m), dim3(ENC_THREADS), gfk_enc_in_smem(m), s, GfkArgT<true>{gfk_dev(m)});
-    else
-      hipLaunchKernelGGL((gfk_enc_in_k<true, false, 1>), dim3(m->bmax), dim3(ENC_THREADS), gfk_enc_in_smem(m), s, GfkArgT<false>{*m});
-    return (int)hipGetLastError();
-  }
-  if (m->H[0] <= 64) {                           // narrow, weights from L2 (large K plans)
-    if (m->n_batch > 1)
-      hipLaunchKernelGGL((gfk_enc_in_k<false, true, 1>), gfk_grid(dim3(m->bmax), m), dim3(ENC_THREADS), gfk_enc_in_smem(m), s, GfkArgT<true>{gfk_dev(m)});
-    else
-      hipLaunchKernelGGL((gfk_enc_in_k<false, false, 1>), dim3(m->bmax), dim3(ENC_THREADS), gfk_enc_in_smem(m), s, GfkArgT<false>{*m});
-    return (int)hipGetLastError();
-  }
-  if (m->stage_flags & 1)
-    do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_enc_in_k<true, true>), gfk_grid(dim3(m->bmax), m), dim3(ENC_THREADS), gfk_enc_in_smem(m), s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_enc_in_k<true, false>), dim3(m->bmax), dim3(ENC_THREADS), gfk_enc_in_smem(m), s, GfkArgT<false>{*m}); } while (0);
-  else
-    do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_enc_in_k<false, true>), gfk_grid(dim3(m->bmax), m), dim3(ENC_THREADS), gfk_enc_in_smem(m), s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_enc_in_k<false, false>), dim3(m->bmax), dim3(ENC_THREADS), gfk_enc_in_smem(m), s, GfkArgT<false>{*m}); } while (0);
-  return (int)hipGetLastError();
+  // narrow: two workgroups per CU when staged, else the weights from L2 (large K plans)
+  return gfk_launch(gfk_find(kEncIn, m->stage_flags & 1, m->H[0] <= 64), m, dim3(m->bmax),
+                    dim3(ENC_THREADS), gfk_enc_in_smem(m), s);
 }
 
 extern "C" int gfk_enc_in_set_smem(size_t bytes) {
-  // the attribute is per function and process-wide: only ever raise it, so an engine
-  // built earlier with a larger footprint keeps launching after a smaller one is set up
   static size_t cur = 0;
-  if (bytes <= cur) return 0;
-  cur = bytes;
-  const void* ks[] = {(const void*)gfk_enc_in_k<true>, (const void*)gfk_enc_in_k<true, true>, (const void*)gfk_enc_in_k<false>, (const void*)gfk_enc_in_k<false, true>,
-                      (const void*)gfk_enc_in_k<true, false, 1>,
-                      (const void*)gfk_enc_in_k<true, true, 1>, (const void*)gfk_enc_in_k<false, false, 1>,
-                      (const void*)gfk_enc_in_k<false, true, 1>};
-  for (const void* k : ks) {
-    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) return (int)e;
-  }
-  return 0;
+  return gfk_lds_raised(cur, bytes) ? gfk_raise_lds(kEncIn, bytes) : 0;
 }
 
 extern "C" size_t gfk_enc_weight_bytes(const GfkModel* m) {

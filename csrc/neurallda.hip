@@ -13,6 +13,7 @@
 // which equals sum_b theta_d[b,k] dtheta_d[b,k] and is computed from the tiny
 // [B, K] tensors in lda_beta_bwd's prologue instead of a V-wide reduction.
 #include "gfk_common.h"
+#include "gfk_launch.h"
 
 using namespace gfk;
 
@@ -466,49 +467,38 @@ extern "C" size_t gfk_lda_bwd_smem(const GfkModel* m) {
   return sizeof(float) * lda_bwd_floats(m, lda_bwd_th_lds(m));
 }
 
+// The instance tables (csrc/gfk_launch.h): a launcher looks its kernel up by the key it
+// computes from the model, and gfk_lda_set_smem raises the dynamic-LDS limit of the same
+// rows.  A new instance is one new row.
+// the beta kernels: {LDA_FWD, K <= 64} | {LDA_BWD, theta_d in LDS, chunked rows}
+enum { LDA_FWD, LDA_BWD };
+static const GfkRow kLdaBeta[] = {
+    {{LDA_FWD, 0}, {gfk_lda_beta_fwd<false>, gfk_lda_beta_fwd<true>}},
+    {{LDA_FWD, 1}, {gfk_lda_beta_fwd<false, 64>, gfk_lda_beta_fwd<true, 64>}},
+    {{LDA_BWD, 1, 0}, {gfk_lda_beta_bwd_k<true, false>, gfk_lda_beta_bwd_k<true, true>}},
+    {{LDA_BWD, 0, 0}, {gfk_lda_beta_bwd_k<false, false>, gfk_lda_beta_bwd_k<false, true>}},
+    {{LDA_BWD, 0, 1}, {gfk_lda_beta_bwd_k<false, false, true>, gfk_lda_beta_bwd_k<false, true, true>}}};
+// the row kernel: {64-topic units}  (a few KB of LDS: never raised)
+static const GfkRow kLdaRow[] = {{{1}, GFK_PAIR(gfk_lda_row_k, 1)}, {{2}, GFK_PAIR(gfk_lda_row_k, 2)},
+                                 {{3}, GFK_PAIR(gfk_lda_row_k, 3)}, {{4}, GFK_PAIR(gfk_lda_row_k, 4)}};
+
 extern "C" int gfk_launch_lda_beta_fwd(const GfkModel* m, hipStream_t s) {
-  if (m->K <= 64)
-    do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_lda_beta_fwd<true, 64>), gfk_grid(dim3(m->dec_grid), m), dim3(LBT), gfk_lda_fwd_smem(m->K), s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_lda_beta_fwd<false, 64>), dim3(m->dec_grid), dim3(LBT), gfk_lda_fwd_smem(m->K), s, GfkArgT<false>{*m}); } while (0);
-  else
-    do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_lda_beta_fwd<true>), gfk_grid(dim3(m->dec_grid), m), dim3(LBT), gfk_lda_fwd_smem(m->K), s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_lda_beta_fwd<false>), dim3(m->dec_grid), dim3(LBT), gfk_lda_fwd_smem(m->K), s, GfkArgT<false>{*m}); } while (0);
-  return (int)hipGetLastError();
+  return gfk_launch(gfk_find(kLdaBeta, LDA_FWD, m->K <= 64), m, dim3(m->dec_grid), dim3(LBT),
+                    gfk_lda_fwd_smem(m->K), s);
 }
 
 extern "C" int gfk_launch_lda_row(const GfkModel* m, hipStream_t s) {
-  const dim3 g(m->bmax), t(LDA_ROW_THREADS);
-  const size_t sm = gfk_lda_row_smem(m->K);
-  const int kq = (m->K + 63) / 64;
-  if (kq <= 1) do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_lda_row_k<1, true>), gfk_grid(g, m), t, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_lda_row_k<1, false>), g, t, sm, s, GfkArgT<false>{*m}); } while (0);
-  else if (kq == 2) do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_lda_row_k<2, true>), gfk_grid(g, m), t, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_lda_row_k<2, false>), g, t, sm, s, GfkArgT<false>{*m}); } while (0);
-  else if (kq == 3) do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_lda_row_k<3, true>), gfk_grid(g, m), t, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_lda_row_k<3, false>), g, t, sm, s, GfkArgT<false>{*m}); } while (0);
-  else do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_lda_row_k<4, true>), gfk_grid(g, m), t, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_lda_row_k<4, false>), g, t, sm, s, GfkArgT<false>{*m}); } while (0);
-  return (int)hipGetLastError();
+  return gfk_launch(gfk_find(kLdaRow, (m->K + 63) / 64), m, dim3(m->bmax), dim3(LDA_ROW_THREADS),
+                    gfk_lda_row_smem(m->K), s);
 }
 
 extern "C" int gfk_launch_lda_beta_bwd(const GfkModel* m, hipStream_t s) {
-  const dim3 g(m->dec_grid), t(LBT);
-  if (m->bmax > LDA_XB)
-    do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_lda_beta_bwd_k<false, true, true>), gfk_grid(g, m), t, gfk_lda_bwd_smem(m), s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_lda_beta_bwd_k<false, false, true>), g, t, gfk_lda_bwd_smem(m), s, GfkArgT<false>{*m}); } while (0);
-  else if (lda_bwd_th_lds(m))
-    do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_lda_beta_bwd_k<true, true>), gfk_grid(g, m), t, gfk_lda_bwd_smem(m), s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_lda_beta_bwd_k<true, false>), g, t, gfk_lda_bwd_smem(m), s, GfkArgT<false>{*m}); } while (0);
-  else
-    do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_lda_beta_bwd_k<false, true>), gfk_grid(g, m), t, gfk_lda_bwd_smem(m), s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_lda_beta_bwd_k<false, false>), g, t, gfk_lda_bwd_smem(m), s, GfkArgT<false>{*m}); } while (0);
-  return (int)hipGetLastError();
+  // (more rows than one chunk: never with theta_d in LDS -- lda_bwd_th_lds)
+  return gfk_launch(gfk_find(kLdaBeta, LDA_BWD, lda_bwd_th_lds(m), m->bmax > LDA_XB), m, dim3(m->dec_grid),
+                    dim3(LBT), gfk_lda_bwd_smem(m), s);
 }
 
 extern "C" int gfk_lda_set_smem(size_t bytes) {
-  // the attribute is per function and process-wide: only ever raise it, so an engine
-  // built earlier with a larger footprint keeps launching after a smaller one is set up
   static size_t cur = 0;
-  if (bytes <= cur) return 0;
-  cur = bytes;
-  const void* ks[] = {(const void*)gfk_lda_beta_fwd<false>, (const void*)gfk_lda_beta_fwd<true>,
-                      (const void*)gfk_lda_beta_fwd<false, 64>, (const void*)gfk_lda_beta_fwd<true, 64>, (const void*)gfk_lda_beta_bwd_k<true>, (const void*)gfk_lda_beta_bwd_k<true, true>,
-                      (const void*)gfk_lda_beta_bwd_k<false>, (const void*)gfk_lda_beta_bwd_k<false, true>,
-                      (const void*)gfk_lda_beta_bwd_k<false, false, true>, (const void*)gfk_lda_beta_bwd_k<false, true, true>};
-  for (const void* k : ks) {
-    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) return (int)e;
-  }
-  return 0;
+  return gfk_lds_raised(cur, bytes) ? gfk_raise_lds(kLdaBeta, bytes) : 0;
 }

@@ -26,6 +26,7 @@
 //               layer.  Workgroup 0: prior gradients, the loss, the step counter.
 #define GFK_BATCHED_COPY 1   // batched kernels copy their descriptor (gfk_common.h gfk_model)
 #include "gfk_common.h"
+#include "gfk_launch.h"
 
 using namespace gfk;
 
@@ -1335,32 +1336,60 @@ __global__ void __launch_bounds__(FT) gfk_post_colstats_lb_k(GfkArgT<false> ga) 
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// The instance tables (csrc/gfk_launch.h): a launcher looks its kernel up by the key it
+// computes from the model, and gfk_post_set_smem raises the dynamic-LDS limit of the same
+// rows.  A new instance is one new row.
+// ---------------------------------------------------------------------------------------
+// post_fwd: {batch in LDS, 0 | the large-batch instance's k quarters (one client)}
+static const GfkRow kPostFwd[] = {{{1, 0}, {gfk_post_fwd_k<true, false>, gfk_post_fwd_k<true, true>}},
+                                  {{0, 0}, {gfk_post_fwd_k<false, false>, gfk_post_fwd_k<false, true>}},
+                                  {{0, 4}, {gfk_post_fwd_k<false, false, true>, nullptr}},
+                                  {{0, 8}, {gfk_post_fwd_k<false, false, true, 8>, nullptr}}};
+
+// row_bwd: {64-topic units}; 8 (K <= 512) is the large-batch plan's, one client
+static const GfkRow kRowBwd[] = {{{1}, GFK_PAIR(gfk_row_bwd_k, 1)}, {{2}, GFK_PAIR(gfk_row_bwd_k, 2)},
+                                 {{3}, GFK_PAIR(gfk_row_bwd_k, 3)}, {{4}, GFK_PAIR(gfk_row_bwd_k, 4)},
+                                 {{8}, {gfk_row_bwd_k<8, false>, nullptr}}};
+
+// post_bwd: {batch in LDS, staged weights, shape}.  The shapes: one row per workgroup; the
+// large-batch one (one client, never in LDS); two rows one after the other, and 2 / 4 rows
+// through each phase together (batched launches only)
+enum { POST_PLAIN, POST_LB, POST_SERIAL2, POST_JOINT2, POST_JOINT4 };
+#define POST_BWD_ROWS(L, ST)                                                                         \
+  {{L, ST, POST_PLAIN}, {gfk_post_bwd_k<L, ST, false>, gfk_post_bwd_k<L, ST, true>}},                \
+  {{L, ST, POST_SERIAL2}, {nullptr, gfk_post_bwd_k<L, ST, true, false, 2>}},                         \
+  {{L, ST, POST_JOINT2}, {nullptr, gfk_post_bwd_k<L, ST, true, false, 2, true>}},                    \
+  {{L, ST, POST_JOINT4}, {nullptr, gfk_post_bwd_k<L, ST, true, false, 4, true>}}
+static const GfkRow kPostBwd[] = {POST_BWD_ROWS(true, true), POST_BWD_ROWS(true, false),
+                                  POST_BWD_ROWS(false, true), POST_BWD_ROWS(false, false),
+                                  {{false, true, POST_LB}, {gfk_post_bwd_k<false, true, false, true>, nullptr}},
+                                  {{false, false, POST_LB}, {gfk_post_bwd_k<false, false, false, true>, nullptr}}};
+#undef POST_BWD_ROWS
+
+// the large-batch column statistics (one client): {backward}  (static LDS only)
+static const GfkRow kColstatsLb[] = {{{0}, {gfk_post_colstats_lb_k<false>, nullptr}},
+                                     {{1}, {gfk_post_colstats_lb_k<true>, nullptr}}};
+
+// the batch bookkeeping: {prep 0 / docs 1}  (no LDS)
+static const GfkRow kBatch[] = {{{0}, {gfk_batch_prep<false>, gfk_batch_prep<true>}},
+                                {{1}, {gfk_batch_docs<false>, gfk_batch_docs<true>}}};
+
 static int launch_colstats_lb(const GfkModel* m, hipStream_t s, bool bwd) {
   if (m->n_batch > 1 || !m->ws_colstat) return -1;
-  const dim3 g((2 * m->K + 63) / 64);
-  if (bwd) hipLaunchKernelGGL((gfk_post_colstats_lb_k<true>), g, dim3(FT), 0, s, GfkArgT<false>{*m});
-  else hipLaunchKernelGGL((gfk_post_colstats_lb_k<false>), g, dim3(FT), 0, s, GfkArgT<false>{*m});
-  return (int)hipGetLastError();
+  return gfk_launch(gfk_find(kColstatsLb, bwd), m, dim3((2 * m->K + 63) / 64), dim3(FT), 0, s);
 }
 
 extern "C" int gfk_launch_post_fwd(const GfkModel* m, hipStream_t s) {
+  const dim3 g(m->bmax), t(FT);
   if (m->stage_flags & GFK_LB) {        // large batches: statistics once, then the rows
     if (batch_in_lds(*m)) return -1;
     const int e = launch_colstats_lb(m, s, false);
     if (e) return e;
-    if (m->K <= 256)
-      hipLaunchKernelGGL((gfk_post_fwd_k<false, false, true>), dim3(m->bmax), dim3(FT), gfk_post_fwd_smem(m), s, GfkArgT<false>{*m});
-    else if (m->K <= 512)
-      hipLaunchKernelGGL((gfk_post_fwd_k<false, false, true, 8>), dim3(m->bmax), dim3(FT), gfk_post_fwd_smem(m), s, GfkArgT<false>{*m});
-    else
-      return -1;
-    return (int)hipGetLastError();
+    if (m->K > 512) return -1;
+    return gfk_launch(gfk_find(kPostFwd, 0, m->K <= 256 ? 4 : 8), m, g, t, gfk_post_fwd_smem(m), s);
   }
-  if (batch_in_lds(*m))
-    do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_post_fwd_k<true, true>), gfk_grid(dim3(m->bmax), m), dim3(FT), gfk_post_fwd_smem(m), s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_post_fwd_k<true, false>), dim3(m->bmax), dim3(FT), gfk_post_fwd_smem(m), s, GfkArgT<false>{*m}); } while (0);
-  else
-    do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_post_fwd_k<false, true>), gfk_grid(dim3(m->bmax), m), dim3(FT), gfk_post_fwd_smem(m), s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_post_fwd_k<false, false>), dim3(m->bmax), dim3(FT), gfk_post_fwd_smem(m), s, GfkArgT<false>{*m}); } while (0);
-  return (int)hipGetLastError();
+  return gfk_launch(gfk_find(kPostFwd, batch_in_lds(*m), 0), m, g, t, gfk_post_fwd_smem(m), s);
 }
 
 extern "C" int gfk_launch_post_bwd(const GfkModel* m, hipStream_t s) {
@@ -1370,105 +1399,47 @@ extern "C" int gfk_launch_post_bwd(const GfkModel* m, hipStream_t s) {
   if (moved && (m->n_batch < 2 || (m->stage_flags & GFK_LB))) return -1;
   const dim3 g(m->bmax + (moved ? 1 : 0)), t(PT);
   const size_t sm = gfk_row_bwd_smem(m);
-  if (kq <= 1) do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_row_bwd_k<1, true>), gfk_grid(g, m), t, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_row_bwd_k<1, false>), g, t, sm, s, GfkArgT<false>{*m}); } while (0);
-  else if (kq == 2) do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_row_bwd_k<2, true>), gfk_grid(g, m), t, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_row_bwd_k<2, false>), g, t, sm, s, GfkArgT<false>{*m}); } while (0);
-  else if (kq == 3) do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_row_bwd_k<3, true>), gfk_grid(g, m), t, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_row_bwd_k<3, false>), g, t, sm, s, GfkArgT<false>{*m}); } while (0);
-  else if (kq > 4) {                   // K <= 512 (the large-batch plan; one client)
-    if (kq > 8 || m->n_batch > 1) return -1;
-    hipLaunchKernelGGL((gfk_row_bwd_k<8, false>), g, t, sm, s, GfkArgT<false>{*m});
-  }
-  else do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_row_bwd_k<4, true>), gfk_grid(g, m), t, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_row_bwd_k<4, false>), g, t, sm, s, GfkArgT<false>{*m}); } while (0);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
+  if (kq > 4 && (kq > 8 || m->n_batch > 1)) return -1;   // K <= 512 (the large-batch plan; one client)
+  const int e = gfk_launch(gfk_find(kRowBwd, kq > 4 ? 8 : kq), m, g, t, sm, s);
+  if (e) return e;
   const dim3 gb(m->bmax + (moved ? 0 : 1)), tb(FT);   // + the prior / loss / step workgroup
   const size_t sb = gfk_post_bwd_smem(m);
-  const bool st = m->stage_flags & 1;
+  const bool st = m->stage_flags & 1, inl = batch_in_lds(*m);
   const bool joint = m->stage_flags & GFK_POST_JOINT, rows4 = m->stage_flags & GFK_POST_ROWS4;
   if ((joint && !moved) || (rows4 && !joint)) return -1;
   if (joint) {
     // R rows per workgroup, through each phase together (batched launches)
     const int R = rows4 ? 4 : 2;
-    const dim3 gj = gfk_grid(dim3((m->bmax + R - 1) / R), m);
-    const GfkArgT<true> a{gfk_dev(m)};
-    const int inst = (batch_in_lds(*m) ? 4 : 0) | (st ? 2 : 0) | (rows4 ? 1 : 0);
-    switch (inst) {
-      case 7: hipLaunchKernelGGL((gfk_post_bwd_k<true, true, true, false, 4, true>), gj, tb, sb, s, a); break;
-      case 6: hipLaunchKernelGGL((gfk_post_bwd_k<true, true, true, false, 2, true>), gj, tb, sb, s, a); break;
-      case 5: hipLaunchKernelGGL((gfk_post_bwd_k<true, false, true, false, 4, true>), gj, tb, sb, s, a); break;
-      case 4: hipLaunchKernelGGL((gfk_post_bwd_k<true, false, true, false, 2, true>), gj, tb, sb, s, a); break;
-      case 3: hipLaunchKernelGGL((gfk_post_bwd_k<false, true, true, false, 4, true>), gj, tb, sb, s, a); break;
-      case 2: hipLaunchKernelGGL((gfk_post_bwd_k<false, true, true, false, 2, true>), gj, tb, sb, s, a); break;
-      case 1: hipLaunchKernelGGL((gfk_post_bwd_k<false, false, true, false, 4, true>), gj, tb, sb, s, a); break;
-      default: hipLaunchKernelGGL((gfk_post_bwd_k<false, false, true, false, 2, true>), gj, tb, sb, s, a); break;
-    }
-    return (int)hipGetLastError();
+    return gfk_launch(gfk_find(kPostBwd, inl, st, rows4 ? POST_JOINT4 : POST_JOINT2), m,
+                      dim3((m->bmax + R - 1) / R), tb, sb, s);
   }
-  if (moved) {
-    // two rows per workgroup, one after the other (batched launches)
-    const dim3 g2((m->bmax + 1) / 2 + (moved ? 0 : 1));
-    const GfkArgT<true> a{gfk_dev(m)};
-    if (batch_in_lds(*m)) {
-      if (st) hipLaunchKernelGGL((gfk_post_bwd_k<true, true, true, false, 2>), gfk_grid(g2, m), tb, sb, s, a);
-      else hipLaunchKernelGGL((gfk_post_bwd_k<true, false, true, false, 2>), gfk_grid(g2, m), tb, sb, s, a);
-    } else {
-      if (st) hipLaunchKernelGGL((gfk_post_bwd_k<false, true, true, false, 2>), gfk_grid(g2, m), tb, sb, s, a);
-      else hipLaunchKernelGGL((gfk_post_bwd_k<false, false, true, false, 2>), gfk_grid(g2, m), tb, sb, s, a);
-    }
-    return (int)hipGetLastError();
-  }
+  if (moved)   // two rows per workgroup, one after the other (batched launches)
+    return gfk_launch(gfk_find(kPostBwd, inl, st, POST_SERIAL2), m, dim3((m->bmax + 1) / 2), tb, sb, s);
   if (m->stage_flags & GFK_LB) {        // large batches: the column sums once, then the rows
-    if (batch_in_lds(*m)) return -1;
+    if (inl) return -1;
     const int e2 = launch_colstats_lb(m, s, true);
     if (e2) return e2;
-    if (st) hipLaunchKernelGGL((gfk_post_bwd_k<false, true, false, true>), gb, tb, sb, s, GfkArgT<false>{*m});
-    else hipLaunchKernelGGL((gfk_post_bwd_k<false, false, false, true>), gb, tb, sb, s, GfkArgT<false>{*m});
-    return (int)hipGetLastError();
+    return gfk_launch(gfk_find(kPostBwd, false, st, POST_LB), m, gb, tb, sb, s);
   }
-  if (batch_in_lds(*m)) {
-    if (st) do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_post_bwd_k<true, true, true>), gfk_grid(gb, m), tb, sb, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_post_bwd_k<true, true, false>), gb, tb, sb, s, GfkArgT<false>{*m}); } while (0);
-    else do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_post_bwd_k<true, false, true>), gfk_grid(gb, m), tb, sb, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_post_bwd_k<true, false, false>), gb, tb, sb, s, GfkArgT<false>{*m}); } while (0);
-  } else {
-    if (st) do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_post_bwd_k<false, true, true>), gfk_grid(gb, m), tb, sb, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_post_bwd_k<false, true, false>), gb, tb, sb, s, GfkArgT<false>{*m}); } while (0);
-    else do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_post_bwd_k<false, false, true>), gfk_grid(gb, m), tb, sb, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_post_bwd_k<false, false, false>), gb, tb, sb, s, GfkArgT<false>{*m}); } while (0);
-  }
-  return (int)hipGetLastError();
+  return gfk_launch(gfk_find(kPostBwd, inl, st, POST_PLAIN), m, gb, tb, sb, s);
 }
 
 extern "C" int gfk_launch_batch_prep(const GfkModel* m, hipStream_t s) {
-  do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_batch_prep<true>), gfk_grid(dim3(1), m), dim3(256), 0, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_batch_prep<false>), dim3(1), dim3(256), 0, s, GfkArgT<false>{*m}); } while (0);
-  return (int)hipGetLastError();
+  return gfk_launch(gfk_find(kBatch, 0), m, dim3(1), dim3(256), 0, s);
 }
 
 extern "C" int gfk_launch_batch_docs(const GfkModel* m, hipStream_t s) {
-  do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_batch_docs<true>), gfk_grid(dim3(1), m), dim3(256), 0, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_batch_docs<false>), dim3(1), dim3(256), 0, s, GfkArgT<false>{*m}); } while (0);
-  return (int)hipGetLastError();
+  return gfk_launch(gfk_find(kBatch, 1), m, dim3(1), dim3(256), 0, s);
 }
 
+// (the dynamic-LDS tables; kColstatsLb and kBatch are launched with none)
 extern "C" int gfk_post_set_smem(size_t bytes) {
-  // the attribute is per function and process-wide: only ever raise it, so an engine
-  // built earlier with a larger footprint keeps launching after a smaller one is set up
   static size_t cur = 0;
-  if (bytes <= cur) return 0;
-  cur = bytes;
-  const void* ks[] = {(const void*)gfk_post_fwd_k<true>, (const void*)gfk_post_fwd_k<true, true>, (const void*)gfk_post_fwd_k<false>, (const void*)gfk_post_fwd_k<false, true>,
-                      (const void*)gfk_row_bwd_k<1>, (const void*)gfk_row_bwd_k<1, true>, (const void*)gfk_row_bwd_k<2>, (const void*)gfk_row_bwd_k<2, true>,
-                      (const void*)gfk_row_bwd_k<3>, (const void*)gfk_row_bwd_k<3, true>, (const void*)gfk_row_bwd_k<4>, (const void*)gfk_row_bwd_k<4, true>,
-                      (const void*)gfk_post_bwd_k<true, true>, (const void*)gfk_post_bwd_k<true, true, true>, (const void*)gfk_post_bwd_k<true, false>, (const void*)gfk_post_bwd_k<true, false, true>,
-                      (const void*)gfk_post_bwd_k<false, true>, (const void*)gfk_post_bwd_k<false, true, true>, (const void*)gfk_post_bwd_k<false, false>, (const void*)gfk_post_bwd_k<false, false, true>,
-                      (const void*)gfk_post_fwd_k<false, false, true>, (const void*)gfk_post_fwd_k<false, false, true, 8>,
-                      (const void*)gfk_row_bwd_k<8>, (const void*)gfk_post_bwd_k<false, true, false, true>,
-                      (const void*)gfk_post_bwd_k<false, false, false, true>,
-                      (const void*)gfk_post_bwd_k<true, true, true, false, 2>, (const void*)gfk_post_bwd_k<true, false, true, false, 2>,
-                      (const void*)gfk_post_bwd_k<false, true, true, false, 2>, (const void*)gfk_post_bwd_k<false, false, true, false, 2>,
-                      (const void*)gfk_post_bwd_k<true, true, true, false, 2, true>, (const void*)gfk_post_bwd_k<true, false, true, false, 2, true>,
-                      (const void*)gfk_post_bwd_k<false, true, true, false, 2, true>, (const void*)gfk_post_bwd_k<false, false, true, false, 2, true>,
-                      (const void*)gfk_post_bwd_k<true, true, true, false, 4, true>, (const void*)gfk_post_bwd_k<true, false, true, false, 4, true>,
-                      (const void*)gfk_post_bwd_k<false, true, true, false, 4, true>, (const void*)gfk_post_bwd_k<false, false, true, false, 4, true>};
-  for (const void* k : ks) {
-    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) return (int)e;
-  }
-  return 0;
+  if (!gfk_lds_raised(cur, bytes)) return 0;
+  int e = gfk_raise_lds(kPostFwd, bytes);
+  if (!e) e = gfk_raise_lds(kRowBwd, bytes);
+  if (!e) e = gfk_raise_lds(kPostBwd, bytes);
+  return e;
 }
 
 extern "C" size_t gfk_post_smem(const GfkModel* m) {

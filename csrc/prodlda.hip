@@ -38,6 +38,7 @@
 // [dec_grid * 4][bmax][2] (one partial per forward wave column strip).
 #define GFK_BATCHED_COPY 1   // batched kernels copy their descriptor (gfk_common.h gfk_model)
 #include "gfk_common.h"
+#include "gfk_launch.h"
 
 using namespace gfk;
 
@@ -2804,8 +2805,71 @@ extern "C" size_t gfk_prodlda_bwd_smem(const GfkModel* m) {
   return bwd_smem(m, bwd_kq(*m));
 }
 
+// ---------------------------------------------------------------------------------------
+// The instance tables (csrc/gfk_launch.h): a launcher looks its kernel up by the key it
+// computes from the model, and gfk_prodlda_set_smem raises the dynamic-LDS limit of the
+// same rows.  A new instance is one new row.
+// ---------------------------------------------------------------------------------------
+// tile forward: {bmax, bf16}
+#define FWD_ROW(BM, BF) {{BM, BF}, GFK_PAIR(prodlda_fwd_kernel, BM, BF)}
+static const GfkRow kFwdTile[] = {FWD_ROW(16, false), FWD_ROW(32, false), FWD_ROW(64, false), FWD_ROW(128, false),
+                                  FWD_ROW(16, true),  FWD_ROW(32, true),  FWD_ROW(64, true),  FWD_ROW(128, true)};
+#undef FWD_ROW
+
+// strip forward: {bmax, k pairs (strip_np / strip_np_bf), bf16, postfold}; the postfold
+// instances exist for 8 pairs only (gfk_postfold: K <= 64)
+#define STRIP_ROW(BM, NP, BF, FP)                                       \
+  {{BM, NP, BF, FP}, {prodlda_fwd_strip_kernel<BM, NP, 3, false, BF, FP>, \
+                      prodlda_fwd_strip_kernel<BM, NP, 3, true, BF, FP>}}
+#define STRIP_ROWS(BM)                                                                             \
+  STRIP_ROW(BM, 8, false, false), STRIP_ROW(BM, 13, false, false), STRIP_ROW(BM, 16, false, false), \
+  STRIP_ROW(BM, 25, false, false), STRIP_ROW(BM, 26, false, false), STRIP_ROW(BM, 32, false, false), \
+  STRIP_ROW(BM, 8, true, false), STRIP_ROW(BM, 16, true, false), STRIP_ROW(BM, 32, true, false),   \
+  STRIP_ROW(BM, 8, false, true), STRIP_ROW(BM, 8, true, true)
+static const GfkRow kFwdStrip[] = {STRIP_ROWS(16), STRIP_ROWS(32), STRIP_ROWS(64)};
+#undef STRIP_ROWS
+#undef STRIP_ROW
+
+// backward: {kernel, bmax, 64-topic units (K + 63) / 64, flag}.  kernel: the tile backward
+// by its k ranges (1 / 4; flag = bf16), the k-range backward reading the stored logit
+// gradient (pre2; flag = bf16), the pipelined one (flag = fused update, bmax 64 only)
+enum { BWD_PRE2 = 2, BWD_PIPE = 3 };    // (1, 4: the tile backward's KQ)
+#define BWD_ROWS_B(BM, U, BF)                                          \
+  {{1, BM, U, BF}, GFK_PAIR(prodlda_bwd_kernel, BM, U, 1, BF)},        \
+  {{4, BM, U, BF}, GFK_PAIR(prodlda_bwd_kernel, BM, U, 4, BF)}
+#define BWD_ROWS_P(BM, U, BF) {{BWD_PRE2, BM, U, BF}, GFK_PAIR(prodlda_bwd_pre2_kernel, BM, U, BF)}
+#define BWD_ROWS_F(U, BF)                                                                         \
+  BWD_ROWS_B(16, U, BF), BWD_ROWS_B(32, U, BF), BWD_ROWS_B(64, U, BF), BWD_ROWS_B(128, U, BF),    \
+  BWD_ROWS_P(16, U, BF), BWD_ROWS_P(32, U, BF), BWD_ROWS_P(64, U, BF),                            \
+  {{BWD_PIPE, 64, U, BF}, GFK_PAIR(prodlda_bwd_pipe_kernel, 64, U, BF)}
+#define BWD_ROWS(U) BWD_ROWS_F(U, false), BWD_ROWS_F(U, true)
+static const GfkRow kBwd[] = {BWD_ROWS(1), BWD_ROWS(2), BWD_ROWS(3), BWD_ROWS(4)};
+#undef BWD_ROWS
+#undef BWD_ROWS_F
+#undef BWD_ROWS_P
+#undef BWD_ROWS_B
+
+// the logit gradient ahead of the pre2 / pipelined backward: {bmax}  (static LDS only)
+static const GfkRow kDlogit[] = {{{16}, GFK_PAIR(prodlda_dlogit_kernel, 16)},
+                                 {{32}, GFK_PAIR(prodlda_dlogit_kernel, 32)},
+                                 {{64}, GFK_PAIR(prodlda_dlogit_kernel, 64)}};
+
+// the fused large-batch decoder (one client): {forward 0 / backward 1, k tiles of the instance}
+static const GfkRow kLbFused[] = {{{0, 16}, {prodlda_lb_fwd_kernel<16>, nullptr}},
+                                  {{0, 32}, {prodlda_lb_fwd_kernel<32>, nullptr}},
+                                  {{0, 52}, {prodlda_lb_fwd_kernel<52>, nullptr}},
+                                  {{1, 4}, {prodlda_lb_bwd_kernel<4, 16>, nullptr}},
+                                  {{1, 8}, {prodlda_lb_bwd_kernel<8, 16>, nullptr}},
+                                  {{1, 13}, {prodlda_lb_bwd_kernel<13, 16>, nullptr}}};
+
+// the large-batch column kernels around the GEMMs: {colbn 0 / dlogit 1, bmax}  (static LDS only)
+#define LB_ROWS(BM) {{0, BM}, GFK_PAIR(prodlda_lb_colbn_kernel, BM)}, {{1, BM}, GFK_PAIR(prodlda_lb_dlogit_kernel, BM)}
+static const GfkRow kLbCol[] = {LB_ROWS(16), LB_ROWS(32), LB_ROWS(64), LB_ROWS(128), LB_ROWS(256), LB_ROWS(512)};
+#undef LB_ROWS
+
+static const GfkRow kRowLoss[] = {{{0}, {gfk_prodlda_row_loss<false>, gfk_prodlda_row_loss<true>}}};
+
 // the large-batch kernels (stage_flags GFK_LB): bmax 256 or 512, ws_dt the [bmax][ldb] matrix
-#define GFK_LB_LAUNCH(KERN, BM)                                                                      do { if (m->n_batch > 1) hipLaunchKernelGGL((KERN<BM, true>), gfk_grid(dim3(m->dec_grid), m), dim3(LB_THREADS), 0, s, GfkArgT<true>{gfk_dev(m)});        else hipLaunchKernelGGL((KERN<BM, false>), dim3(m->dec_grid), dim3(LB_THREADS), 0, s, GfkArgT<false>{*m}); } while (0)
 static int launch_lb(const GfkModel* m, hipStream_t s, bool fwd) {
   if (m->bmax < 16 || m->bmax > 512 || (m->bmax & (m->bmax - 1)) || m->dec_grid < 1 || m->ldb < m->V ||
       m->n_batch > 1)
@@ -2814,43 +2878,19 @@ static int launch_lb(const GfkModel* m, hipStream_t s, bool fwd) {
   if (fwd && (m->lb_fused & 1)) {
     if (m->bmax != 256 || m->K > 208 || m->kind != GFK_PRODLDA) return -1;
     const size_t sm = sizeof(float) * lb_fwd_lds_floats(m->K);
-    const dim3 g(m->dec_grid), b(LBF_NT);
-    if (m->K <= 64) hipLaunchKernelGGL((prodlda_lb_fwd_kernel<16>), g, b, sm, s, GfkArgT<false>{*m});
-    else if (m->K <= 128) hipLaunchKernelGGL((prodlda_lb_fwd_kernel<32>), g, b, sm, s, GfkArgT<false>{*m});
-    else hipLaunchKernelGGL((prodlda_lb_fwd_kernel<52>), g, b, sm, s, GfkArgT<false>{*m});
-    return (int)hipGetLastError();
+    return gfk_launch(gfk_find(kLbFused, 0, m->K <= 64 ? 16 : m->K <= 128 ? 32 : 52), m,
+                      dim3(m->dec_grid), dim3(LBF_NT), sm, s);
   }
   if (!fwd && (m->lb_fused & 2)) {
     if (m->bmax != 256 || m->K > 208 || m->update_mode != 0 || m->n_dpart != m->dec_grid) return -1;
     const size_t sm = sizeof(float) * lb_bwd_lds_floats(m->K);
-    if (m->K <= 64) hipLaunchKernelGGL((prodlda_lb_bwd_kernel<4, 16>), dim3(m->dec_grid), dim3(1024), sm, s, GfkArgT<false>{*m});
-    else if (m->K <= 128) hipLaunchKernelGGL((prodlda_lb_bwd_kernel<8, 16>), dim3(m->dec_grid), dim3(1024), sm, s, GfkArgT<false>{*m});
-    else hipLaunchKernelGGL((prodlda_lb_bwd_kernel<13, 16>), dim3(m->dec_grid), dim3(1024), sm, s, GfkArgT<false>{*m});
-    return (int)hipGetLastError();
+    return gfk_launch(gfk_find(kLbFused, 1, m->K <= 64 ? 4 : m->K <= 128 ? 8 : 13), m,
+                      dim3(m->dec_grid), dim3(1024), sm, s);
   }
   if (!m->ws_dt) return -1;
-  if (fwd) {
-    switch (m->bmax) {               // (below 256: K > 256 at the batch's own size)
-      case 16: GFK_LB_LAUNCH(prodlda_lb_colbn_kernel, 16); break;
-      case 32: GFK_LB_LAUNCH(prodlda_lb_colbn_kernel, 32); break;
-      case 64: GFK_LB_LAUNCH(prodlda_lb_colbn_kernel, 64); break;
-      case 128: GFK_LB_LAUNCH(prodlda_lb_colbn_kernel, 128); break;
-      case 256: GFK_LB_LAUNCH(prodlda_lb_colbn_kernel, 256); break;
-      default: GFK_LB_LAUNCH(prodlda_lb_colbn_kernel, 512); break;
-    }
-  } else {
-    switch (m->bmax) {
-      case 16: GFK_LB_LAUNCH(prodlda_lb_dlogit_kernel, 16); break;
-      case 32: GFK_LB_LAUNCH(prodlda_lb_dlogit_kernel, 32); break;
-      case 64: GFK_LB_LAUNCH(prodlda_lb_dlogit_kernel, 64); break;
-      case 128: GFK_LB_LAUNCH(prodlda_lb_dlogit_kernel, 128); break;
-      case 256: GFK_LB_LAUNCH(prodlda_lb_dlogit_kernel, 256); break;
-      default: GFK_LB_LAUNCH(prodlda_lb_dlogit_kernel, 512); break;
-    }
-  }
-  return (int)hipGetLastError();
+  // (bmax below 256: K > 256 at the batch's own size)
+  return gfk_launch(gfk_find(kLbCol, fwd ? 0 : 1, m->bmax), m, dim3(m->dec_grid), dim3(LB_THREADS), 0, s);
 }
-#undef GFK_LB_LAUNCH
 
 extern "C" int gfk_launch_prodlda_fwd(const GfkModel* m, hipStream_t s) {
   if (m->stage_flags & GFK_LB) return launch_lb(m, s, true);
@@ -2858,191 +2898,48 @@ extern "C" int gfk_launch_prodlda_fwd(const GfkModel* m, hipStream_t s) {
   dim3 g(m->dec_grid), blk(DEC_THREADS);
   if (m->stage_flags & FWD_STRIP) {
     // fp32, B <= 64, K <= 256; the partial slots need 4 * grid <= 4 * n_tiles
-    const int np = strip_np(m->K);
     if (m->bmax > 64 || m->K > 256 || m->dec_grid > m->n_tiles ||
         (int64_t)m->K * m->ldb >= (1LL << 29)) return -1;
-    const bool fp = strip_postfold(*m);
-    if (m->mm_bf16) {
-      const int nb = strip_np_bf(m->K);
-#define GFK_FWSB(BM, NP)                                                                       \
-      do { if (m->n_batch > 1) hipLaunchKernelGGL((prodlda_fwd_strip_kernel<BM, NP, 3, true, true>), gfk_grid(g, m), dim3(strip_threads(3, NP)), sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((prodlda_fwd_strip_kernel<BM, NP, 3, false, true>), g, dim3(strip_threads(3, NP)), sm, s, GfkArgT<false>{*m}); } while (0)
-#define GFK_FWSB_FP(BM)                                                                        \
-      do { if (m->n_batch > 1) hipLaunchKernelGGL((prodlda_fwd_strip_kernel<BM, 8, 3, true, true, true>), gfk_grid(g, m), dim3(1024), sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((prodlda_fwd_strip_kernel<BM, 8, 3, false, true, true>), g, dim3(1024), sm, s, GfkArgT<false>{*m}); } while (0)
-#define GFK_FWSB_B(BM) if (fp) GFK_FWSB_FP(BM); else if (nb == 8) GFK_FWSB(BM, 8); else if (nb == 16) GFK_FWSB(BM, 16); else GFK_FWSB(BM, 32)
-      switch (m->bmax) {
-        case 16: GFK_FWSB_B(16); break;
-        case 32: GFK_FWSB_B(32); break;
-        default: GFK_FWSB_B(64); break;
-      }
-#undef GFK_FWSB_B
-#undef GFK_FWSB_FP
-#undef GFK_FWSB
-      return (int)hipGetLastError();
-    }
-#define GFK_FWS(BM, NP)                                                                        \
-    do {                                                                                       \
-      if (NP == 8 && fp)                                                                       \
-        do { if (m->n_batch > 1) hipLaunchKernelGGL((prodlda_fwd_strip_kernel<BM, 8, 3, true, false, true>), gfk_grid(g, m), dim3(1024), sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((prodlda_fwd_strip_kernel<BM, 8, 3, false, false, true>), g, dim3(1024), sm, s, GfkArgT<false>{*m}); } while (0); \
-      else                                                                                     \
-        do { if (m->n_batch > 1) hipLaunchKernelGGL((prodlda_fwd_strip_kernel<BM, NP, 3, true>), gfk_grid(g, m), dim3(strip_threads(3, NP)), sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((prodlda_fwd_strip_kernel<BM, NP, 3, false>), g, dim3(strip_threads(3, NP)), sm, s, GfkArgT<false>{*m}); } while (0); \
-    } while (0)
-#define GFK_FWS_B(BM)                                                      \
-    if (np == 8) GFK_FWS(BM, 8);                                           \
-    else if (np == 13) GFK_FWS(BM, 13);                                    \
-    else if (np == 16) GFK_FWS(BM, 16);                                    \
-    else if (np == 25) GFK_FWS(BM, 25);                                    \
-    else if (np == 26) GFK_FWS(BM, 26);                                    \
-    else GFK_FWS(BM, 32)
-    switch (m->bmax) {
-      case 16: GFK_FWS_B(16); break;
-      case 32: GFK_FWS_B(32); break;
-      default: GFK_FWS_B(64); break;
-    }
-#undef GFK_FWS_B
-#undef GFK_FWS
-    return (int)hipGetLastError();
+    const bool bf = m->mm_bf16;
+    const int np = bf ? strip_np_bf(m->K) : strip_np(m->K);
+    return gfk_launch(gfk_find(kFwdStrip, m->bmax, np, bf, strip_postfold(*m)), m, g,
+                      dim3(strip_threads(3, np)), sm, s);
   }
-#define GFK_FWD(BM)                                                                  \
-  if (m->mm_bf16) do { if (m->n_batch > 1) hipLaunchKernelGGL((prodlda_fwd_kernel<BM, true, true>), gfk_grid(g, m), blk, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((prodlda_fwd_kernel<BM, true, false>), g, blk, sm, s, GfkArgT<false>{*m}); } while (0);   \
-  else do { if (m->n_batch > 1) hipLaunchKernelGGL((prodlda_fwd_kernel<BM, false, true>), gfk_grid(g, m), blk, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((prodlda_fwd_kernel<BM, false, false>), g, blk, sm, s, GfkArgT<false>{*m}); } while (0)
-  switch (m->bmax) {
-    case 16: GFK_FWD(16); break;
-    case 32: GFK_FWD(32); break;
-    case 64: GFK_FWD(64); break;
-    case 128: GFK_FWD(128); break;
-    default: return -1;
-  }
-#undef GFK_FWD
-  return (int)hipGetLastError();
-}
-
-template <int MAXU, int KQ, bool BF, bool PRE>
-static void launch_bwd_p(const GfkModel* m, dim3 g, size_t sm, hipStream_t s) {
-  const dim3 blk(KQ == 1 ? DEC_THREADS : 512);
-  // (the pipelined backward also serves mm_bf16: its GEMMs keep fp32 operands -- the
-  // kernel is bound by its beta / Adam-state HBM traffic, not by the matrix cores)
-  if constexpr (PRE) {
-    if (bwd_pipe(*m)) {
-      if (m->update_mode == 1) {
-        if (m->n_batch > 1) hipLaunchKernelGGL((prodlda_bwd_pipe_kernel<64, MAXU, true, true>), gfk_grid(g, m), blk, sm, s, GfkArgT<true>{gfk_dev(m)});
-        else hipLaunchKernelGGL((prodlda_bwd_pipe_kernel<64, MAXU, true, false>), g, blk, sm, s, GfkArgT<false>{*m});
-      } else {
-        if (m->n_batch > 1) hipLaunchKernelGGL((prodlda_bwd_pipe_kernel<64, MAXU, false, true>), gfk_grid(g, m), blk, sm, s, GfkArgT<true>{gfk_dev(m)});
-        else hipLaunchKernelGGL((prodlda_bwd_pipe_kernel<64, MAXU, false, false>), g, blk, sm, s, GfkArgT<false>{*m});
-      }
-      return;
-    }
-  }
-  if (PRE) {
-    switch (m->bmax) {
-      case 16: do { if (m->n_batch > 1) hipLaunchKernelGGL((prodlda_bwd_pre2_kernel<16, MAXU, BF, true>), gfk_grid(g, m), blk, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((prodlda_bwd_pre2_kernel<16, MAXU, BF, false>), g, blk, sm, s, GfkArgT<false>{*m}); } while (0); break;
-      case 32: do { if (m->n_batch > 1) hipLaunchKernelGGL((prodlda_bwd_pre2_kernel<32, MAXU, BF, true>), gfk_grid(g, m), blk, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((prodlda_bwd_pre2_kernel<32, MAXU, BF, false>), g, blk, sm, s, GfkArgT<false>{*m}); } while (0); break;
-      default: do { if (m->n_batch > 1) hipLaunchKernelGGL((prodlda_bwd_pre2_kernel<64, MAXU, BF, true>), gfk_grid(g, m), blk, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((prodlda_bwd_pre2_kernel<64, MAXU, BF, false>), g, blk, sm, s, GfkArgT<false>{*m}); } while (0); break;
-    }
-    return;
-  }
-  switch (m->bmax) {
-    case 16: do { if (m->n_batch > 1) hipLaunchKernelGGL((prodlda_bwd_kernel<16, MAXU, KQ, BF, true>), gfk_grid(g, m), blk, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((prodlda_bwd_kernel<16, MAXU, KQ, BF, false>), g, blk, sm, s, GfkArgT<false>{*m}); } while (0); break;
-    case 32: do { if (m->n_batch > 1) hipLaunchKernelGGL((prodlda_bwd_kernel<32, MAXU, KQ, BF, true>), gfk_grid(g, m), blk, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((prodlda_bwd_kernel<32, MAXU, KQ, BF, false>), g, blk, sm, s, GfkArgT<false>{*m}); } while (0); break;
-    case 64: do { if (m->n_batch > 1) hipLaunchKernelGGL((prodlda_bwd_kernel<64, MAXU, KQ, BF, true>), gfk_grid(g, m), blk, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((prodlda_bwd_kernel<64, MAXU, KQ, BF, false>), g, blk, sm, s, GfkArgT<false>{*m}); } while (0); break;
-    default: do { if (m->n_batch > 1) hipLaunchKernelGGL((prodlda_bwd_kernel<128, MAXU, KQ, BF, true>), gfk_grid(g, m), blk, sm, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((prodlda_bwd_kernel<128, MAXU, KQ, BF, false>), g, blk, sm, s, GfkArgT<false>{*m}); } while (0); break;
-  }
-}
-
-template <int MAXU, int KQ, bool BF>
-static void launch_bwd_b(const GfkModel* m, dim3 g, size_t sm, hipStream_t s) {
-  if (KQ == 4 && m->bwd_pre && m->bmax <= 64) {      // (static LDS: B <= 64)
-    const dim3 gd(m->n_tiles), bd(256);
-    switch (m->bmax) {
-      case 16: do { if (m->n_batch > 1) hipLaunchKernelGGL((prodlda_dlogit_kernel<16, true>), gfk_grid(gd, m), bd, 0, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((prodlda_dlogit_kernel<16, false>), gd, bd, 0, s, GfkArgT<false>{*m}); } while (0); break;
-      case 32: do { if (m->n_batch > 1) hipLaunchKernelGGL((prodlda_dlogit_kernel<32, true>), gfk_grid(gd, m), bd, 0, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((prodlda_dlogit_kernel<32, false>), gd, bd, 0, s, GfkArgT<false>{*m}); } while (0); break;
-      default: do { if (m->n_batch > 1) hipLaunchKernelGGL((prodlda_dlogit_kernel<64, true>), gfk_grid(gd, m), bd, 0, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((prodlda_dlogit_kernel<64, false>), gd, bd, 0, s, GfkArgT<false>{*m}); } while (0); break;
-    }
-    launch_bwd_p<MAXU, KQ, BF, KQ == 4>(m, g, sm, s);
-  } else {
-    launch_bwd_p<MAXU, KQ, BF, false>(m, g, sm, s);
-  }
-}
-
-template <int MAXU, int KQ>
-static void launch_bwd_t(const GfkModel* m, dim3 g, size_t sm, hipStream_t s) {
-  if (m->mm_bf16) launch_bwd_b<MAXU, KQ, true>(m, g, sm, s);
-  else launch_bwd_b<MAXU, KQ, false>(m, g, sm, s);
-}
-
-template <int MAXU>
-static void launch_bwd(const GfkModel* m, hipStream_t s) {
-  const int kq = bwd_kq(*m);
-  const int slabs = m->n_dpart < m->n_tiles ? m->n_dpart : m->n_tiles;
-  const size_t sm = bwd_smem(m, kq);
-  if (kq == 4) launch_bwd_t<MAXU, 4>(m, dim3(4 * slabs), sm, s);
-  else launch_bwd_t<MAXU, 1>(m, dim3(slabs), sm, s);
+  return gfk_launch(gfk_find(kFwdTile, m->bmax, (bool)m->mm_bf16), m, g, blk, sm, s);
 }
 
 extern "C" int gfk_launch_prodlda_bwd(const GfkModel* m, hipStream_t s) {
   if (m->stage_flags & GFK_LB) return launch_lb(m, s, false);
   if (m->bmax != 16 && m->bmax != 32 && m->bmax != 64 && m->bmax != 128) return -1;
   if ((int64_t)m->K * m->ldb * 4 >= 0x7FFF0000LL) return -1;   // 32-bit buffer offsets
-  switch ((m->K + 63) / 64) {
-    case 1: launch_bwd<1>(m, s); break;
-    case 2: launch_bwd<2>(m, s); break;
-    case 3: launch_bwd<3>(m, s); break;
-    default: launch_bwd<4>(m, s); break;
+  const int maxu = (m->K + 63) / 64;
+  const int kq = bwd_kq(*m);
+  const int slabs = m->n_dpart < m->n_tiles ? m->n_dpart : m->n_tiles;
+  const size_t sm = bwd_smem(m, kq);
+  const dim3 g(kq == 4 ? 4 * slabs : slabs), blk(kq == 1 ? DEC_THREADS : 512);
+  const bool bf = m->mm_bf16;
+  if (kq == 4 && m->bwd_pre && m->bmax <= 64) {      // (static LDS: B <= 64)
+    const int e = gfk_launch(gfk_find(kDlogit, m->bmax), m, dim3(m->n_tiles), dim3(256), 0, s);
+    if (e) return e;
+    // (the pipelined backward also serves mm_bf16: its GEMMs keep fp32 operands -- the
+    // kernel is bound by its beta / Adam-state HBM traffic, not by the matrix cores)
+    if (bwd_pipe(*m)) return gfk_launch(gfk_find(kBwd, BWD_PIPE, 64, maxu, m->update_mode == 1), m, g, blk, sm, s);
+    return gfk_launch(gfk_find(kBwd, BWD_PRE2, m->bmax, maxu, bf), m, g, blk, sm, s);
   }
-  return (int)hipGetLastError();
+  return gfk_launch(gfk_find(kBwd, kq, m->bmax, maxu, bf), m, g, blk, sm, s);
 }
 
 extern "C" int gfk_launch_prodlda_row_loss(const GfkModel* m, hipStream_t s) {
-  do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_prodlda_row_loss<true>), gfk_grid(dim3(m->bmax), m), dim3(64), 0, s, GfkArgT<true>{gfk_dev(m)}); else hipLaunchKernelGGL((gfk_prodlda_row_loss<false>), dim3(m->bmax), dim3(64), 0, s, GfkArgT<false>{*m}); } while (0);
-  return (int)hipGetLastError();
+  return gfk_launch(gfk_find(kRowLoss, 0), m, dim3(m->bmax), dim3(64), 0, s);
 }
 
+// (the dynamic-LDS tables; kDlogit, kLbCol and kRowLoss are launched with none)
 extern "C" int gfk_prodlda_set_smem(size_t bytes) {
-  // the attribute is per function and process-wide: only ever raise it, so an engine
-  // built earlier with a larger footprint keeps launching after a smaller one is set up
   static size_t cur = 0;
-  if (bytes <= cur) return 0;
-  cur = bytes;
-  const void* ks[] = {(const void*)prodlda_fwd_kernel<16, false>, (const void*)prodlda_fwd_kernel<16, false, true>, (const void*)prodlda_fwd_kernel<32, false>, (const void*)prodlda_fwd_kernel<32, false, true>,
-                      (const void*)prodlda_fwd_kernel<64, false>, (const void*)prodlda_fwd_kernel<64, false, true>, (const void*)prodlda_fwd_kernel<128, false>, (const void*)prodlda_fwd_kernel<128, false, true>,
-                      (const void*)prodlda_fwd_kernel<16, true>, (const void*)prodlda_fwd_kernel<16, true, true>, (const void*)prodlda_fwd_kernel<32, true>, (const void*)prodlda_fwd_kernel<32, true, true>,
-                      (const void*)prodlda_fwd_kernel<64, true>, (const void*)prodlda_fwd_kernel<64, true, true>, (const void*)prodlda_fwd_kernel<128, true>, (const void*)prodlda_fwd_kernel<128, true, true>,
-#define GFK_FWS_PTRS1(BM, F) (const void*)prodlda_fwd_strip_kernel<BM, 8, F>, (const void*)prodlda_fwd_strip_kernel<BM, 8, F, true>, \
-    (const void*)prodlda_fwd_strip_kernel<BM, 13, F>, (const void*)prodlda_fwd_strip_kernel<BM, 13, F, true>, (const void*)prodlda_fwd_strip_kernel<BM, 16, F>, (const void*)prodlda_fwd_strip_kernel<BM, 16, F, true>, \
-    (const void*)prodlda_fwd_strip_kernel<BM, 25, F>, (const void*)prodlda_fwd_strip_kernel<BM, 25, F, true>, \
-    (const void*)prodlda_fwd_strip_kernel<BM, 26, F>, (const void*)prodlda_fwd_strip_kernel<BM, 26, F, true>, (const void*)prodlda_fwd_strip_kernel<BM, 32, F>, (const void*)prodlda_fwd_strip_kernel<BM, 32, F, true>
-#define GFK_FWS_PTRSB(BM) (const void*)prodlda_fwd_strip_kernel<BM, 8, 3, false, true>, (const void*)prodlda_fwd_strip_kernel<BM, 8, 3, true, true>, \
-    (const void*)prodlda_fwd_strip_kernel<BM, 16, 3, false, true>, (const void*)prodlda_fwd_strip_kernel<BM, 16, 3, true, true>, \
-    (const void*)prodlda_fwd_strip_kernel<BM, 32, 3, false, true>, (const void*)prodlda_fwd_strip_kernel<BM, 32, 3, true, true>
-#define GFK_FWS_PTRSF(BM) (const void*)prodlda_fwd_strip_kernel<BM, 8, 3, false, false, true>, (const void*)prodlda_fwd_strip_kernel<BM, 8, 3, true, false, true>, \
-    (const void*)prodlda_fwd_strip_kernel<BM, 8, 3, false, true, true>, (const void*)prodlda_fwd_strip_kernel<BM, 8, 3, true, true, true>
-#define GFK_FWS_PTRS(BM) GFK_FWS_PTRS1(BM, 3), GFK_FWS_PTRSB(BM), GFK_FWS_PTRSF(BM)
-                      GFK_FWS_PTRS(16), GFK_FWS_PTRS(32), GFK_FWS_PTRS(64),
-#undef GFK_FWS_PTRS
-#undef GFK_FWS_PTRSF
-#undef GFK_FWS_PTRSB
-#undef GFK_FWS_PTRS1
-#define GFK_BWD_PTRS2(U, T, F) (const void*)prodlda_bwd_kernel<16, U, T, F>, (const void*)prodlda_bwd_kernel<16, U, T, F, true>, \
-    (const void*)prodlda_bwd_kernel<32, U, T, F>, (const void*)prodlda_bwd_kernel<32, U, T, F, true>, (const void*)prodlda_bwd_kernel<64, U, T, F>, (const void*)prodlda_bwd_kernel<64, U, T, F, true>, \
-    (const void*)prodlda_bwd_kernel<128, U, T, F>, (const void*)prodlda_bwd_kernel<128, U, T, F, true>
-#define GFK_BWD_PTRS1(U, T) GFK_BWD_PTRS2(U, T, false), GFK_BWD_PTRS2(U, T, true)
-#define GFK_BWD_PTRS3(U, F) (const void*)prodlda_bwd_pre2_kernel<16, U, F>, (const void*)prodlda_bwd_pre2_kernel<16, U, F, true>, (const void*)prodlda_bwd_pre2_kernel<32, U, F>, (const void*)prodlda_bwd_pre2_kernel<32, U, F, true>, \
-    (const void*)prodlda_bwd_pre2_kernel<64, U, F>, (const void*)prodlda_bwd_pre2_kernel<64, U, F, true>
-#define GFK_BWD_PTRS(U) GFK_BWD_PTRS1(U, 1), GFK_BWD_PTRS1(U, 4), GFK_BWD_PTRS3(U, false), \
-    GFK_BWD_PTRS3(U, true), (const void*)prodlda_bwd_pipe_kernel<64, U, false>, (const void*)prodlda_bwd_pipe_kernel<64, U, false, true>, \
-    (const void*)prodlda_bwd_pipe_kernel<64, U, true>, (const void*)prodlda_bwd_pipe_kernel<64, U, true, true>
-                      GFK_BWD_PTRS(1), GFK_BWD_PTRS(2), GFK_BWD_PTRS(3), GFK_BWD_PTRS(4),
-                      (const void*)prodlda_lb_bwd_kernel<4, 16>, (const void*)prodlda_lb_bwd_kernel<8, 16>,
-                      (const void*)prodlda_lb_bwd_kernel<13, 16>,
-                      (const void*)prodlda_lb_fwd_kernel<16>, (const void*)prodlda_lb_fwd_kernel<32>,
-                      (const void*)prodlda_lb_fwd_kernel<52>};
-#undef GFK_BWD_PTRS
-#undef GFK_BWD_PTRS3
-#undef GFK_BWD_PTRS1
-#undef GFK_BWD_PTRS2
-  for (const void* k : ks) {
-    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) return (int)e;
-  }
-  return 0;
+  if (!gfk_lds_raised(cur, bytes)) return 0;
+  int e = gfk_raise_lds(kFwdTile, bytes);
+  if (!e) e = gfk_raise_lds(kFwdStrip, bytes);
+  if (!e) e = gfk_raise_lds(kBwd, bytes);
+  if (!e) e = gfk_raise_lds(kLbFused, bytes);
+  return e;
 }

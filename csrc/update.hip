@@ -24,6 +24,7 @@
 // One extra workgroup prepares the next minibatch (gfk_common.h).
 #define GFK_BATCHED_COPY 1   // batched kernels copy their descriptor (gfk_common.h gfk_model)
 #include "gfk_common.h"
+#include "gfk_launch.h"
 
 using namespace gfk;
 
@@ -967,31 +968,25 @@ static bool win_sparse_vl(const GfkModel* m) {
   return need <= gfk_win_update_smem(m);
 }
 
-#define GFK_WIN_SPARSE_LAUNCH(VL, CTX)                                                               \
-  do {                                                                                           \
-    if (m->n_batch > 1)                                                                          \
-      hipLaunchKernelGGL((gfk_win_sparse_k<512, true, VL, CTX>), gfk_grid(gs, m), dim3(512),     \
-                         gfk_win_update_smem(m), s, GfkArgT<true>{gfk_dev(m)},                   \
-                         GfkUArgT<true>{reinterpret_cast<const GfkUpdate*>(m->dev_upd)});        \
-    else                                                                                         \
-      hipLaunchKernelGGL((gfk_win_sparse_k<512, false, VL, CTX>), gs, dim3(512),                 \
-                         gfk_win_update_smem(m), s, GfkArgT<false>{*m}, GfkUArgT<false>{*u});    \
-  } while (0)
-
-#define GFK_WIN_SPARSE_LB_LAUNCH()                                                                   \
-  do {                                                                                           \
-    constexpr int RSL = GFK_BMAX_LIMIT / 64;                                                     \
-    if (m->n_batch > 1)                                                                          \
-      hipLaunchKernelGGL((gfk_win_sparse_k<512, true, false, false, RSL>), gfk_grid(gs, m),     \
-                         dim3(512), gfk_win_update_smem(m), s, GfkArgT<true>{gfk_dev(m)},        \
-                         GfkUArgT<true>{reinterpret_cast<const GfkUpdate*>(m->dev_upd)});        \
-    else                                                                                         \
-      hipLaunchKernelGGL((gfk_win_sparse_k<512, false, false, false, RSL>), gs, dim3(512),       \
-                         gfk_win_update_smem(m), s, GfkArgT<false>{*m}, GfkUArgT<false>{*u});    \
-  } while (0)
+// The instance table (csrc/gfk_launch.h): the launcher looks its kernel up by the key it
+// computes from the model, and gfk_win_update_set_smem raises the dynamic-LDS limit of the
+// same rows.  A new instance is one new row.
+// {kernel, threads} the dense tiles | {kernel, LDS second moment, contextual tiles, large batch}
+// the sparse tiles | {kernel} the large-batch chunked dense tiles (one client)
+enum { WINK_DENSE, WINK_SPARSE, WINK_LB };
+#define WIN_SPARSE_ROW(VL, CTX) {{WINK_SPARSE, VL, CTX}, {gfk_win_sparse_k<512, false, VL, CTX>, gfk_win_sparse_k<512, true, VL, CTX>}}
+static const GfkRowU kWinUpdate[] = {
+    {{WINK_DENSE, 512}, GFK_PAIR(gfk_win_update_k, 512)},
+    {{WINK_DENSE, 1024}, GFK_PAIR(gfk_win_update_k, 1024)},
+    WIN_SPARSE_ROW(false, false), WIN_SPARSE_ROW(true, false), WIN_SPARSE_ROW(false, true), WIN_SPARSE_ROW(true, true),
+    {{WINK_SPARSE, 0, 0, 1}, {gfk_win_sparse_k<512, false, false, false, GFK_BMAX_LIMIT / 64>,
+                              gfk_win_sparse_k<512, true, false, false, GFK_BMAX_LIMIT / 64>}},
+    {{WINK_LB}, {gfk_win_lb_k<1024>, nullptr}}};
+#undef WIN_SPARSE_ROW
 
 extern "C" int gfk_launch_win_update(const GfkModel* m, const GfkUpdate* u, hipStream_t s) {
   const int extra = m->ctx_fused == 1 ? m->n_tiles : (m->ctx_fused == 2 ? (m->C + 63) / 64 : 0);
+  const size_t sm = gfk_win_update_smem(m);
   if (m->stage_flags & WIN_SPARSE) {
     // bag-of-words inputs, or fused CombinedTM (its contextual half as dense tiles after
     // the sparse ones: B <= 64 so the operand blocks fit the kernel's LDS)
@@ -999,33 +994,22 @@ extern "C" int gfk_launch_win_update(const GfkModel* m, const GfkUpdate* u, hipS
     if (m->H[0] > 64 || m->bmax > (comb ? 64 : GFK_BMAX_LIMIT) || !(m->input == GFK_IN_BOW || comb))
       return -1;
     const dim3 gs(u->n_w + u->n_v + 1 + m->n_tiles * (comb ? 2 : 1));
-    if (m->bmax > 128)
-      GFK_WIN_SPARSE_LB_LAUNCH();
-    else if (comb && win_sparse_vl(m))
-      GFK_WIN_SPARSE_LAUNCH(true, true);
-    else if (comb)
-      GFK_WIN_SPARSE_LAUNCH(false, true);
-    else if (win_sparse_vl(m))
-      GFK_WIN_SPARSE_LAUNCH(true, false);
-    else
-      GFK_WIN_SPARSE_LAUNCH(false, false);
-    return (int)hipGetLastError();
+    // (the large-batch instance: never with the LDS second moment -- win_sparse_vl -- nor
+    // with contextual tiles -- comb: B <= 64)
+    return gfk_launch(gfk_find(kWinUpdate, WINK_SPARSE, win_sparse_vl(m), comb, m->bmax > 128), m, u, gs,
+                      dim3(512), sm, s);
   }
   if (m->bmax > 128) {                 // large batches: the chunked dense tiles
     if (m->H[0] > 64 || m->update_mode != 0 || m->input != GFK_IN_BOW || m->n_batch > 1) return -1;
     const dim3 gl(u->n_w + u->n_v + 1 + m->n_tiles);
-    hipLaunchKernelGGL((gfk_win_lb_k<1024>), gl, dim3(1024), gfk_win_update_smem(m), s, GfkArgT<false>{*m}, GfkUArgT<false>{*u});
-    return (int)hipGetLastError();
+    return gfk_launch(gfk_find(kWinUpdate, WINK_LB), m, u, gl, dim3(1024), sm, s);
   }
   const dim3 g(m->n_tiles + u->n_w + u->n_v + 1 + extra);
   // more W_in tiles than two rounds of 16-wave workgroups (dec_grid = the CUs' slots), or the
   // batched launch of several clients' tiles asks for the 8-wave shape (stage_flags bit 9,
   // set by BatchedSteps when all clients' tiles together exceed two rounds)
-  if ((m->n_tiles > 2 * m->dec_grid && m->n_tiles > 512) || (m->stage_flags & WIN_BATCH8))
-    do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_win_update_k<512, true>), gfk_grid(g, m), dim3(512), gfk_win_update_smem(m), s, GfkArgT<true>{gfk_dev(m)}, GfkUArgT<true>{reinterpret_cast<const GfkUpdate*>(m->dev_upd)}); else hipLaunchKernelGGL((gfk_win_update_k<512, false>), g, dim3(512), gfk_win_update_smem(m), s, GfkArgT<false>{*m}, GfkUArgT<false>{*u}); } while (0);
-  else
-    do { if (m->n_batch > 1) hipLaunchKernelGGL((gfk_win_update_k<1024, true>), gfk_grid(g, m), dim3(1024), gfk_win_update_smem(m), s, GfkArgT<true>{gfk_dev(m)}, GfkUArgT<true>{reinterpret_cast<const GfkUpdate*>(m->dev_upd)}); else hipLaunchKernelGGL((gfk_win_update_k<1024, false>), g, dim3(1024), gfk_win_update_smem(m), s, GfkArgT<false>{*m}, GfkUArgT<false>{*u}); } while (0);
-  return (int)hipGetLastError();
+  const int nt = ((m->n_tiles > 2 * m->dec_grid && m->n_tiles > 512) || (m->stage_flags & WIN_BATCH8)) ? 512 : 1024;
+  return gfk_launch(gfk_find(kWinUpdate, WINK_DENSE, nt), m, u, g, dim3(nt), sm, s);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1485,23 +1469,6 @@ extern "C" int gfk_win_fold_launch(const GfkModel* m0, const GfkUpdate* u0, cons
 }
 
 extern "C" int gfk_win_update_set_smem(size_t bytes) {
-  // the attribute is per function and process-wide: only ever raise it, so an engine
-  // built earlier with a larger footprint keeps launching after a smaller one is set up
   static size_t cur = 0;
-  if (bytes <= cur) return 0;
-  cur = bytes;
-  const void* ks[] = {(const void*)gfk_win_update_k<512, false>, (const void*)gfk_win_update_k<512, true>,
-                      (const void*)gfk_win_update_k<1024, false>, (const void*)gfk_win_update_k<1024, true>,
-                      (const void*)gfk_win_sparse_k<512, false>, (const void*)gfk_win_sparse_k<512, true>,
-                      (const void*)gfk_win_sparse_k<512, false, true>, (const void*)gfk_win_sparse_k<512, true, true>,
-                      (const void*)gfk_win_sparse_k<512, false, false, true>, (const void*)gfk_win_sparse_k<512, true, false, true>,
-                      (const void*)gfk_win_sparse_k<512, false, true, true>, (const void*)gfk_win_sparse_k<512, true, true, true>,
-                      (const void*)gfk_win_sparse_k<512, false, false, false, GFK_BMAX_LIMIT / 64>,
-                      (const void*)gfk_win_sparse_k<512, true, false, false, GFK_BMAX_LIMIT / 64>,
-                      (const void*)gfk_win_lb_k<1024>};
-  for (const void* k : ks) {
-    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) return (int)e;
-  }
-  return 0;
+  return gfk_lds_raised(cur, bytes) ? gfk_raise_lds(kWinUpdate, bytes) : 0;
 }
