@@ -1085,11 +1085,13 @@ constexpr int LBB_LD = 68;                   // LDS row stride of D / Bt (confli
 // A operands for every k step held in registers for the whole persistent loop (2 KS per lane,
 // KS = ceil(K / 4); theta_d is the same for every tile; 8 waves so that K = 200's 104 of them
 // fit without spills), and the tile's beta rows come by LDS-DMA into one of two
-// buffers (Bs [K][LBF_LD]: the next tile's rows land while this one multiplies), read as the
-// MFMA B operand (4 rows x 16 columns per instruction at stride 80: 64 distinct banks).
+// buffers (Bs [4 ceil(K / 4)][LBF_LD], rows >= K zeroed once: the next tile's rows land while
+// this one multiplies), read as the MFMA B operand (4 rows x 16 columns per instruction at
+// stride 80: 64 distinct banks).
 constexpr int LBF_LD = 80;
 constexpr int LBF_NT = 512;                  // 8 waves (one workgroup per CU: up to 256 VGPRs)
-__host__ __device__ inline int lb_fwd_lds_floats(int K) { return 2 * K * LBF_LD; }
+// (rows padded to whole 4-k MFMA steps: the steps read rows K .. 4 ceil(K / 4) - 1 as B operands)
+__host__ __device__ inline int lb_fwd_lds_floats(int K) { return 2 * ((K + 3) / 4 * 4) * LBF_LD; }
 template <int KS>
 __global__ void __launch_bounds__(LBF_NT) prodlda_lb_fwd_kernel(GfkArgT<false> ga) {
   constexpr int BM = 256, NW = LBF_NT / 64, RTW = BM / 16 / NW;
@@ -1102,7 +1104,14 @@ __global__ void __launch_bounds__(LBF_NT) prodlda_lb_fwd_kernel(GfkArgT<false> g
   const int nks = (K + 3) / 4;
   const float inv_nb = 1.f / (float)nb;
   float* bs0 = smem;
-  float* bs1 = smem + K * LBF_LD;
+  float* bs1 = smem + 4 * nks * LBF_LD;
+  // rows K .. 4 nks - 1 of both buffers: the last k step multiplies them by theta_d's zero
+  // padding, and 0 x (whatever an earlier kernel left in LDS, a NaN or Inf at times) is NaN.
+  // The DMA never writes them: zeroed once (the loop's first barrier orders the stores)
+  for (int i = tid; i < (4 * nks - K) * LBF_LD; i += LBF_NT) {
+    bs0[K * LBF_LD + i] = 0.f;
+    bs1[K * LBF_LD + i] = 0.f;
+  }
   const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)m.beta, 0, K * ldb * 4, 0x00020000);
   if (gfk_bx() == 0 && tid == 0) *m.nbt_beta += 1;
   // beta's rows of a tile -> LDS: wave w copies rows w + NW u (64 columns; past ldb: zeros)
