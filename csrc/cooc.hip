@@ -39,6 +39,7 @@ typedef struct GfkCooc {
   int64_t n_docs;                   // documents of this chunk
   int64_t bits_words;               // capacity of bits, in 64-bit words
   int32_t W, V;
+  int32_t max_grid;                 // > 0: at most this many pack workgroups (tests); 0: below
 } GfkCooc;
 }
 
@@ -150,7 +151,7 @@ extern "C" int gfk_cooc_max_words() { return CO_MAX_W; }
 // Nothing is launched when a check fails.
 extern "C" int gfk_cooc(const GfkCooc* p, hipStream_t s) {
   if (!p) return -7;
-  if (p->W < 1 || p->W > CO_MAX_W || p->V < 1) return -5;
+  if (p->W < 1 || p->W > CO_MAX_W || p->V < 1 || p->max_grid < 0) return -5;
   if (p->n_docs < 0 || p->n_docs >= ((int64_t)1 << 31) - 64) return -6;
   if (!p->indptr || !p->indices || !p->values || !p->slot || !p->bits || !p->counts) return -7;
   if (p->n_docs == 0) return 0;
@@ -162,7 +163,9 @@ extern "C" int gfk_cooc(const GfkCooc* p, hipStream_t s) {
   e = hipFuncSetAttribute((const void*)gfk_cooc_pack_k, hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)smem);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(gfk_cooc_pack_k, dim3(G < 4096 ? G : 4096), dim3(64), smem, s, *p, G);
+  int pgrid = G < 4096 ? G : 4096;           // (the kernel strides over the groups)
+  if (p->max_grid > 0 && pgrid > p->max_grid) pgrid = p->max_grid;
+  hipLaunchKernelGGL(gfk_cooc_pack_k, dim3(pgrid), dim3(64), smem, s, *p, G);
   int rc = (int)hipGetLastError();
   if (rc) return rc;
   // the split of the document axis only sizes the grid: integer sums do not depend on it

@@ -54,6 +54,8 @@ typedef struct GfkScore {
   int32_t n_docs, n_samples;
   uint64_t seed;
   int32_t grid, doc0;    // doc0: global index of the chunk's first document (RNG key)
+  int32_t max_grid;      // > 0: no launch but gfk_score_mean_k gets more workgroups (tests: the
+                         // strided loops take several work items each); 0: the grids below
 } GfkScore;
 }
 
@@ -372,11 +374,11 @@ __global__ void __launch_bounds__(SC_THREADS) gfk_score_mean_k(GfkScore p) {
 }
 
 template <int RT>
-int launch_score(const ScoreArgs& a, const GfkScore* p, size_t smem, hipStream_t s) {
+int launch_score(const ScoreArgs& a, const GfkScore* p, unsigned grid, size_t smem, hipStream_t s) {
   hipError_t e = hipFuncSetAttribute((const void*)gfk_doc_score_k<RT>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(gfk_doc_score_k<RT>, dim3(p->grid), dim3(SC_THREADS), smem, s, a, *p);
+  hipLaunchKernelGGL(gfk_doc_score_k<RT>, dim3(grid), dim3(SC_THREADS), smem, s, a, *p);
   return (int)hipGetLastError();
 }
 
@@ -395,7 +397,8 @@ extern "C" size_t gfk_doc_score_smem(const GfkModel* m) { return sizeof(float) *
 extern "C" int gfk_doc_score(const GfkModel* m, const GfkScore* p, hipStream_t s) {
   if (p->n_docs <= 0) return 0;
   if (m->kind != GFK_PRODLDA) return -2;
-  if (m->K <= 0 || m->K > 64 * SC_KQ || m->V <= 0 || m->ldb < m->V || p->grid <= 0 || p->n_samples < 0)
+  if (m->K <= 0 || m->K > 64 * SC_KQ || m->V <= 0 || m->ldb < m->V || p->grid <= 0 || p->n_samples < 0 ||
+      p->max_grid < 0)
     return -5;
   const int64_t R = p->n_samples > 0 ? p->n_samples : 1;
   if (R * p->n_docs >= ((int64_t)1 << 31)) return -6;
@@ -407,16 +410,21 @@ extern "C" int gfk_doc_score(const GfkModel* m, const GfkScore* p, hipStream_t s
   a.beta = m->beta; a.beta_rm = m->beta_rm; a.beta_rv = m->beta_rv;
   a.prior_mean = m->prior_mean; a.prior_var = m->prior_var;
   a.V = m->V; a.K = m->K; a.ldb = m->ldb; a.bn_eps = m->bn_eps;
+  // max_grid caps the three strided launches (every result is independent of its grid);
+  // gfk_score_mean_k is one thread per document with no loop and keeps its grid
+  const int64_t cap = p->max_grid > 0 ? p->max_grid : ((int64_t)1 << 31);
+  auto capped = [&](int64_t g) { return (unsigned)(g < cap ? g : cap); };
   const int tgrid = (int)((p->n_docs + SC_WAVES - 1) / SC_WAVES < 2048 ? (p->n_docs + SC_WAVES - 1) / SC_WAVES
                                                                        : 2048);
-  hipLaunchKernelGGL(gfk_score_theta_k, dim3(tgrid), dim3(SC_THREADS), 0, s, a, *p);
+  hipLaunchKernelGGL(gfk_score_theta_k, dim3(capped(tgrid)), dim3(SC_THREADS), 0, s, a, *p);
   int rc = (int)hipGetLastError();
   if (rc) return rc;
   const size_t smem = gfk_doc_score_smem(m);
-  rc = sc_row_tiles(m->K) == 4 ? launch_score<4>(a, p, smem, s) : launch_score<2>(a, p, smem, s);
+  const unsigned dgrid = capped(p->grid);
+  rc = sc_row_tiles(m->K) == 4 ? launch_score<4>(a, p, dgrid, smem, s) : launch_score<2>(a, p, dgrid, smem, s);
   if (rc) return rc;
   const int64_t wrows = (R * p->n_docs + SC_WAVES - 1) / SC_WAVES;
-  hipLaunchKernelGGL(gfk_score_sparse_k, dim3((unsigned)(wrows < 8192 ? wrows : 8192)), dim3(SC_THREADS), 0,
+  hipLaunchKernelGGL(gfk_score_sparse_k, dim3(capped(wrows < 8192 ? wrows : 8192)), dim3(SC_THREADS), 0,
                      s, a, *p);
   rc = (int)hipGetLastError();
   if (rc) return rc;

@@ -49,6 +49,7 @@ typedef struct GfkThin {
   int32_t n_docs, K, V, ld, topic;
   int32_t doc0;            // global index of the chunk's first document (RNG key)
   int32_t pass;            // 1: gfk_thin_count_k, 2: gfk_thin_compact_k
+  int32_t max_grid;        // > 0: at most this many workgroups (tests: several rows per wave)
 } GfkThin;
 }
 
@@ -176,7 +177,7 @@ extern "C" int gfk_thin_max_topics() { return TH_MAX_K; }
 extern "C" int gfk_thin(const GfkThin* p, hipStream_t s) {
   if (!p) return -7;
   if (p->n_docs < 0 || p->doc0 < 0 || p->V < 1) return -5;
-  if (p->pass != 1 && p->pass != 2) return -5;
+  if ((p->pass != 1 && p->pass != 2) || p->max_grid < 0) return -5;
   if (!p->indptr || !p->indices || !p->values || !p->kept) return -7;
   const bool want_rest = p->rest_idx != nullptr;
   if ((p->rest_val != nullptr) != want_rest) return -7;
@@ -195,6 +196,7 @@ extern "C" int gfk_thin(const GfkThin* p, hipStream_t s) {
   if (p->n_docs == 0) return 0;
   int grid = (p->n_docs + TH_WAVES - 1) / TH_WAVES;
   if (grid > 8192) grid = 8192;          // (the kernels stride over the documents)
+  if (p->max_grid > 0 && grid > p->max_grid) grid = p->max_grid;
   if (p->pass == 1)
     hipLaunchKernelGGL(gfk_thin_count_k, dim3(grid), dim3(TH_THREADS), 0, s, *p);
   else

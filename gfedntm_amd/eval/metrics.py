@@ -126,7 +126,8 @@ def _host_csr(data) -> sp.csr_matrix:
                           data.indptr.cpu().numpy()), shape=(data.n_docs, data.vocab_size))
 
 
-def _cooccurrence(data, words, engine: Optional[str], chunk: Optional[int]):
+def _cooccurrence(data, words, engine: Optional[str], chunk: Optional[int],
+                  max_grid: Optional[int] = None):
     """(counts, engine used) -- :func:`cooccurrence_counts` plus which implementation ran."""
     from ..data.bow import DeviceCSR
     from ..ops import cooc
@@ -157,7 +158,7 @@ def _cooccurrence(data, words, engine: Optional[str], chunk: Optional[int]):
                 "co-occurrence counts: %d words exceed the kernels' %d, using the host product",
                 int(w.numel()), cooc.max_words())
     if engine == "fused":
-        return cooc.counts(data, w.to(device), chunk), "fused"
+        return cooc.counts(data, w.to(device), chunk, max_grid), "fused"
     if chunk is not None and int(chunk) < 1:
         raise ValueError("chunk must be a positive number of documents")
     xb = (_host_csr(data)[:, w.cpu().numpy()] > 0).astype(np.int64)
@@ -166,7 +167,7 @@ def _cooccurrence(data, words, engine: Optional[str], chunk: Optional[int]):
 
 
 def cooccurrence_counts(data, words: Sequence[int], engine: Optional[str] = None,
-                        chunk: Optional[int] = None) -> torch.Tensor:
+                        chunk: Optional[int] = None, max_grid: Optional[int] = None) -> torch.Tensor:
     """Exact document co-occurrence counts of ``words`` in ``data``: int64 [W, W] on the
     data's device, ``[i][j]`` = documents in which ``words[i]`` and ``words[j]`` both have a
     stored value > 0 (diagonal: document frequency).
@@ -178,8 +179,9 @@ def cooccurrence_counts(data, words: Sequence[int], engine: Optional[str] = None
     (scipy; no dense [D, W] either); None -- fused for a DeviceCSR on a GPU within the
     limit, exact otherwise.  ``chunk``: documents per launch of the fused path (any positive
     number; by default the bit matrix stays at or below 256 MiB).  The counts are integers:
-    neither engine, chunking nor grid changes them."""
-    return _cooccurrence(data, words, engine, chunk)[0]
+    neither engine, chunking nor grid changes them (``max_grid`` caps the fused pack kernel's
+    workgroups: ops/cooc.py)."""
+    return _cooccurrence(data, words, engine, chunk, max_grid)[0]
 
 
 def _federated_cooccurrence(datas, words, group=None, engine: Optional[str] = None):

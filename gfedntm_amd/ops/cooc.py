@@ -31,9 +31,12 @@ def default_chunk(n_words: int) -> int:
 
 
 @torch.no_grad()
-def counts(data: DeviceCSR, words: torch.Tensor, chunk: Optional[int] = None) -> torch.Tensor:
+def counts(data: DeviceCSR, words: torch.Tensor, chunk: Optional[int] = None,
+           max_grid: Optional[int] = None) -> torch.Tensor:
     """``words``: int64 tensor of distinct, in-range vocabulary indices on ``data.device``
-    (checked by the caller, eval/metrics.py)."""
+    (checked by the caller, eval/metrics.py).  ``max_grid`` caps the workgroups of the pack
+    kernel, so each walks several groups of 64 documents (the counting kernel's 2-D grid is a
+    function of the shape and stays); the counts do not depend on it."""
     lib = native.kernels()
     dev = data.device
     W, V, n = int(words.numel()), int(data.vocab_size), int(data.n_docs)
@@ -42,6 +45,8 @@ def counts(data: DeviceCSR, words: torch.Tensor, chunk: Optional[int] = None) ->
     chunk = default_chunk(W) if chunk is None else int(chunk)
     if chunk < 1:
         raise ValueError("chunk must be a positive number of documents")
+    if max_grid is not None and int(max_grid) < 1:
+        raise ValueError("max_grid must be a positive number of workgroups")
     out = torch.zeros(W, W, dtype=torch.int64, device=dev)
     if not n or not W or not data.indices.numel():      # no stored entry: nothing occurs
         return out
@@ -58,6 +63,7 @@ def counts(data: DeviceCSR, words: torch.Tensor, chunk: Optional[int] = None) ->
             p.slot, p.bits, p.counts = slot.data_ptr(), bits.data_ptr(), out.data_ptr()
             p.n_docs, p.bits_words = min(n, d0 + chunk) - d0, words_cap
             p.W, p.V = W, V
+            p.max_grid = 0 if max_grid is None else int(max_grid)
             rc = lib.gfk_cooc(C.byref(p), stream)
             if rc:
                 raise RuntimeError(f"gfk_cooc failed ({rc})")

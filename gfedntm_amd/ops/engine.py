@@ -36,6 +36,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 from ..data.bow import BatchPlan, DeviceCSR
 from ..models.engine import EngineBase
@@ -48,6 +49,9 @@ BMAX_CHOICES = (16, 32, 64, 128, 256, 512)
 # batch sizes above this run the large-batch plan (csrc/gfk_common.h GFK_LB)
 LB_MIN_BMAX = 256
 LDS_LIMIT = 160 * 1024
+# rows of every contextual GEMM of theta inference (_ctx_dense): the smallest default chunk, so
+# CombinedTM's [rows, V] adapt_bert output stays within that chunk's budget
+CTX_INFER_ROWS = 256
 VB = 64
 # stage_flags plans, fastest first: bit 0 = MLP weights staged in LDS (enc_in,
 # post_bwd); bit 1 = the posterior kernels read the [B, K] batch matrices from L2
@@ -167,6 +171,14 @@ def score_supports(tm, explain: bool = False) -> bool:
 
 
 UPDATE_GRAD, UPDATE_FUSED = 0, 1
+
+
+def _max_grid(max_grid) -> int:
+    """A caller's cap on a launch's workgroups (csrc: the max_grid fields), checked."""
+    g = int(max_grid)
+    if g < 1:
+        raise ValueError("max_grid must be a positive number of workgroups")
+    return g
 
 
 def theta_stride(K: int) -> int:
@@ -1292,20 +1304,36 @@ class FusedEngine(EngineBase):
     def _ctx_dense(self, data: DeviceCSR, d0: int, d1: int) -> torch.Tensor:
         """Dense contextual contribution to the input layer for documents [d0, d1):
         adapt_bert + the contextual half of input_layer (CombinedTM) or the whole
-        input layer (ZeroShotTM) -- library GEMMs, as in the step's CTX_FWD."""
+        input layer (ZeroShotTM) -- library GEMMs, as in the step's CTX_FWD.
+
+        The GEMMs always run on CTX_INFER_ROWS rows (the last block zero-padded): the
+        library picks its algorithm -- and with it the summation order -- by the shape, so
+        GEMMs on the slice itself gave a 15-row tail chunk other bits (1e-6 of the scale) than
+        the same documents inside a larger launch.  With one shape a document's row does not
+        depend on the chunking."""
         c = self._ctx
-        x = data.contextual[d0:d1]
-        h = torch.addmm(c["ba"], x, c["Wa"].t()) @ c["Wc"] if "Wa" in c else x @ c["W"]
-        if "Wl" in c:                # CTM label head: the labels are encoder inputs too
-            if data.labels is None:
-                raise ValueError("this model encodes labels: inference data needs them")
-            h = h + data.labels[d0:d1] @ c["Wl"]
-        return h
+        if "Wl" in c and data.labels is None:    # CTM label head: the labels are encoder inputs too
+            raise ValueError("this model encodes labels: inference data needs them")
+        R = CTX_INFER_ROWS
+        out = torch.empty(d1 - d0, int(self._m.H[0]), dtype=torch.float32, device=self.device)
+
+        def block(t, r0, r1):
+            t = t[r0:r1]
+            return t if r1 - r0 == R else F.pad(t, (0, 0, 0, R - (r1 - r0)))
+
+        for r0 in range(d0, d1, R):
+            r1 = min(d1, r0 + R)
+            x = block(data.contextual, r0, r1)
+            h = torch.addmm(c["ba"], x, c["Wa"].t()) @ c["Wc"] if "Wa" in c else x @ c["W"]
+            if "Wl" in c:
+                h = h + block(data.labels, r0, r1) @ c["Wl"]
+            out[r0 - d0:r1 - d0] = h[:r1 - r0]
+        return out
 
     @torch.no_grad()
     def theta_infer(self, data: DeviceCSR, n_samples: int = 20, seed: int = 0,
                     postprocess: bool = False, threshold: float = 3e-3, moments: bool = False,
-                    chunk: Optional[int] = None) -> torch.Tensor:
+                    chunk: Optional[int] = None, max_grid: Optional[int] = None) -> torch.Tensor:
         """Document-topic distribution of every document of ``data`` (csrc/infer.hip):
         the mean over ``n_samples`` draws of softmax(mu + eps * sigma) with the encoder
         in eval mode (running batch-norm statistics, no dropout), evaluated ONCE per
@@ -1313,7 +1341,10 @@ class FusedEngine(EngineBase):
         for every sample, avitm.py:470-523).  ``postprocess`` fuses the theta
         threshold + L1 normalisation (federated_model.py:170-173); ``moments`` returns
         the posterior [D, 2, K] = (mu, log sigma^2) instead.  The draws are keyed by
-        (seed, document index), so the chunking does not change the result."""
+        (seed, document index), so the chunking does not change the result.  ``max_grid``
+        caps the workgroups of a launch (default: the launcher's own grid), so that every
+        wave walks several documents: the result does not depend on it, which is what
+        tests/test_eval_grid_gpu.py checks."""
         K, n = int(self._m.K), int(data.n_docs)
         out = torch.empty(n, 2 * K if moments else K, dtype=torch.float32, device=self.device)
         if n:
@@ -1324,7 +1355,7 @@ class FusedEngine(EngineBase):
             for d0 in range(0, n, chunk):
                 d1 = min(n, d0 + chunk)
                 self._infer_launch(data, d0, d1, out.data_ptr() + 4 * d0 * out.shape[1],
-                                   n_samples, flags, threshold, seed)
+                                   n_samples, flags, threshold, seed, max_grid)
         return out.view(n, 2, K) if moments else out
 
     def _infer_chunk(self) -> int:
@@ -1335,7 +1366,7 @@ class FusedEngine(EngineBase):
         return max(256, min(1 << 16, (1 << 28) // max(int(self._m.V), 1)))
 
     def _infer_launch(self, data: DeviceCSR, d0: int, d1: int, out_ptr: int, n_samples: int,
-                      flags: int, threshold: float, seed: int):
+                      flags: int, threshold: float, seed: int, max_grid: Optional[int] = None):
         """One gfk_theta_infer launch over documents [d0, d1) into ``out_ptr``."""
         m = self._m
         ctx = m.input != abi.IN_BOW
@@ -1353,6 +1384,8 @@ class FusedEngine(EngineBase):
         p.flags = flags
         p.thr, p.seed, p.doc0 = float(threshold), int(seed) % (1 << 64), d0
         p.grid = int(max(1, min(-(-(d1 - d0) // 8), 4 * cu)))   # 8 waves (docs) per WG
+        if max_grid is not None:
+            p.grid = min(p.grid, _max_grid(max_grid))
         self._sync_dev()
         rc = self.lib.gfk_theta_infer(C.byref(m), C.byref(p), stream)
         if rc:
@@ -1360,7 +1393,8 @@ class FusedEngine(EngineBase):
 
     @torch.no_grad()
     def score(self, data: DeviceCSR, n_samples: int = 1, seed: int = 0,
-              chunk: Optional[int] = None, target: Optional[DeviceCSR] = None) -> torch.Tensor:
+              chunk: Optional[int] = None, target: Optional[DeviceCSR] = None,
+              max_grid: Optional[int] = None) -> torch.Tensor:
         """Held-out ELBO terms [D, 2] = (KL, RL) of every document of ``data``
         (csrc/score.hip): the eval-mode encoder once per document (gfk_theta_infer, the
         posterior moments), then the eval-mode ProdLDA decoder over ``n_samples`` draws of
@@ -1370,7 +1404,9 @@ class FusedEngine(EngineBase):
         built and nothing is read back: the result stays on the device.  Draws are keyed by
         (seed, document index), so neither the chunking nor the grid changes the result.
         ``target``: a second CSR of the same documents (document completion, ops/thin.py
-        split): the encoder reads ``data``, the sparse reconstruction term ``target``."""
+        split): the encoder reads ``data``, the sparse reconstruction term ``target``.
+        ``max_grid`` caps the workgroups of every strided launch, the encoder's included (as in
+        ``theta_infer``); the result does not depend on it."""
         score_supports(self.tm, explain=True)
         m, K, n, S = self._m, int(self._m.K), int(data.n_docs), int(n_samples)
         if S < 0:
@@ -1384,7 +1420,10 @@ class FusedEngine(EngineBase):
         if int(data.vocab_size) != int(m.V):
             raise ValueError(f"data has {data.vocab_size} columns, the model {int(m.V)}")
         rec = data if target is None else target
-        if (int(rec.n_docs), int(rec.vocab_size)) != (n, int(m.V)) or rec.device != data.device:
+        # (the tensors' devices: a DeviceCSR built on "cuda" and one a kernel wrote on "cuda:0"
+        # are on one device)
+        if (int(rec.n_docs), int(rec.vocab_size)) != (n, int(m.V)) \
+                or rec.indptr.device != data.indptr.device:
             raise ValueError("target must hold the same documents and columns as data, on its device")
         f = dict(dtype=torch.float32, device=self.device)
         rows = min(n, chunk) * R
@@ -1399,7 +1438,8 @@ class FusedEngine(EngineBase):
         wg_per_cu = max(1, min(4, LDS_LIMIT // max(int(self.lib.gfk_doc_score_smem(C.byref(m))), 1)))
         for d0 in range(0, n, chunk):
             d1 = min(n, d0 + chunk)
-            self._infer_launch(data, d0, d1, mom.data_ptr(), 1, abi.INFER_MOMENTS, 0.0, seed)
+            self._infer_launch(data, d0, d1, mom.data_ptr(), 1, abi.INFER_MOMENTS, 0.0, seed,
+                               max_grid)
             p = abi.GfkScore()
             p.indptr = rec.indptr.data_ptr() + 4 * d0
             p.indices, p.values = rec.indices.data_ptr(), rec.values.data_ptr()
@@ -1408,6 +1448,7 @@ class FusedEngine(EngineBase):
             p.n_docs, p.n_samples = d1 - d0, S
             p.seed, p.doc0 = int(seed) % (1 << 64), d0
             p.grid = int(max(1, min(-(-(d1 - d0) * R // block) * nv, wg_per_cu * cu)))
+            p.max_grid = 0 if max_grid is None else _max_grid(max_grid)
             rc = self.lib.gfk_doc_score(C.byref(m), C.byref(p), stream)
             if rc:
                 raise RuntimeError(f"gfk_doc_score failed ({rc})")

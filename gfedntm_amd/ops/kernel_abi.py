@@ -181,14 +181,14 @@ class GfkScore(C.Structure):
     _fields_ = [("indptr", P), ("indices", P), ("values", P), ("moments", P), ("theta", P),
                 ("lse_part", P), ("rl_rows", P), ("out", P),
                 ("n_docs", C.c_int32), ("n_samples", C.c_int32), ("seed", C.c_uint64),
-                ("grid", C.c_int32), ("doc0", C.c_int32)]
+                ("grid", C.c_int32), ("doc0", C.c_int32), ("max_grid", C.c_int32)]
 
 
 class GfkCooc(C.Structure):
     """word co-occurrence counting launch (csrc/cooc.hip)."""
     _fields_ = [("indptr", P), ("indices", P), ("values", P), ("slot", P), ("bits", P),
                 ("counts", P), ("n_docs", C.c_int64), ("bits_words", C.c_int64),
-                ("W", C.c_int32), ("V", C.c_int32)]
+                ("W", C.c_int32), ("V", C.c_int32), ("max_grid", C.c_int32)]
 
 
 class GfkThin(C.Structure):
@@ -199,7 +199,8 @@ class GfkThin(C.Structure):
                 ("rest_idx", P), ("rest_val", P),
                 ("seed", C.c_uint64), ("rate", C.c_float),
                 ("n_docs", C.c_int32), ("K", C.c_int32), ("V", C.c_int32), ("ld", C.c_int32),
-                ("topic", C.c_int32), ("doc0", C.c_int32), ("pass_", C.c_int32)]
+                ("topic", C.c_int32), ("doc0", C.c_int32), ("pass_", C.c_int32),
+                ("max_grid", C.c_int32)]
 
 
 THIN_COUNT, THIN_COMPACT = 1, 2

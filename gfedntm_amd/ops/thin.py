@@ -179,7 +179,7 @@ def _np(a):
 
 
 @torch.no_grad()
-def _fused(data, seed, rate, thetas, topic_word, topic, want_rest, return_p, chunk):
+def _fused(data, seed, rate, thetas, topic_word, topic, want_rest, return_p, chunk, max_grid=None):
     lib = native.kernels()
     if not isinstance(data, DeviceCSR):
         data = DeviceCSR(data, "cuda")
@@ -188,6 +188,8 @@ def _fused(data, seed, rate, thetas, topic_word, topic, want_rest, return_p, chu
     chunk = DOC_CHUNK if chunk is None else int(chunk)
     if chunk < 1:
         raise ValueError("chunk must be a positive number of documents")
+    if max_grid is not None and int(max_grid) < 1:
+        raise ValueError("max_grid must be a positive number of workgroups")
     i32 = dict(dtype=torch.int32, device=dev)
     f32 = dict(dtype=torch.float32, device=dev)
     if nnz:
@@ -226,6 +228,7 @@ def _fused(data, seed, rate, thetas, topic_word, topic, want_rest, return_p, chu
                 p.kept = ws.data_ptr()
                 p.seed, p.doc0 = int(seed) % (1 << 64), d0
                 p.n_docs, p.V, p.pass_ = min(n, d0 + chunk) - d0, V, pass_
+                p.max_grid = 0 if max_grid is None else int(max_grid)
                 if pass_ == abi.THIN_COUNT:
                     p.n_kept = cnt[0].data_ptr() + 4 * d0
                     p.n_rest = cnt[1].data_ptr() + 4 * d0 if want_rest else None
@@ -257,28 +260,32 @@ def _fused(data, seed, rate, thetas, topic_word, topic, want_rest, return_p, chu
 
 
 # --------------------------------------------------------------------------- public
-def split(data, rate: float, seed: int, engine: Optional[str] = None, chunk: Optional[int] = None):
+def split(data, rate: float, seed: int, engine: Optional[str] = None, chunk: Optional[int] = None,
+          max_grid: Optional[int] = None):
     """``(kept, rest)``: every token lands in ``kept`` with probability ``rate`` and in
     ``rest`` otherwise; rows stay sorted and no zero is stored.  ``rate`` 0 / 1 put
-    everything into one part (the other is an all-empty CSR)."""
+    everything into one part (the other is an all-empty CSR).  ``max_grid`` (fused engine)
+    caps the workgroups of both passes, so every wave walks several rows; the result does
+    not depend on it."""
     rate = float(rate)
     if not 0.0 <= rate <= 1.0:
         raise ValueError("rate must lie in [0, 1]")
     rate = float(np.float32(rate))
     if _engine(engine, data) == "fused":
-        kept, rest = _fused(data, seed, rate, None, None, 0, True, False, chunk)
+        kept, rest = _fused(data, seed, rate, None, None, 0, True, False, chunk, max_grid)
     else:
         kept, rest = _host(data, seed, rate, None, None, 0, True, False)
     return kept, rest
 
 
 def thin_by_topic(data, thetas, topic_word, topic: int, seed: int, engine: Optional[str] = None,
-                  chunk: Optional[int] = None, return_p: bool = False):
+                  chunk: Optional[int] = None, return_p: bool = False,
+                  max_grid: Optional[int] = None):
     """The tokens of ``data`` that topic ``topic`` is responsible for: Binomial(x_dw,
     theta[d, topic] tw[topic, w] / sum_k theta[d, k] tw[k, w]) of every non-zero.
     ``thetas`` [D, K], ``topic_word`` [K, V] (row-major; a column slice of a wider matrix
     keeps its row stride on the fused engine).  ``return_p``: also the responsibilities,
-    one per non-zero of ``data`` in storage order."""
+    one per non-zero of ``data`` in storage order.  ``max_grid``: as in :func:`split`."""
     n = int(data.n_docs if isinstance(data, DeviceCSR) else data.shape[0])
     V = int(data.vocab_size if isinstance(data, DeviceCSR) else data.shape[1])
     if len(thetas.shape) != 2 or len(topic_word.shape) != 2 or thetas.shape[0] != n \
@@ -287,7 +294,8 @@ def thin_by_topic(data, thetas, topic_word, topic: int, seed: int, engine: Optio
     if not 0 <= int(topic) < thetas.shape[1]:
         raise ValueError(f"topic {topic} out of range")
     if _engine(engine, data) == "fused":
-        out = _fused(data, seed, 0.0, thetas, topic_word, int(topic), False, return_p, chunk)
+        out = _fused(data, seed, 0.0, thetas, topic_word, int(topic), False, return_p, chunk,
+                     max_grid)
     else:
         out = _host(data, seed, 0.0, thetas, topic_word, int(topic), False, return_p)
     return tuple(out) if return_p else out[0]

@@ -29,6 +29,66 @@ def random_csr(n_docs, V, nnz_per_row, seed=0):
     return m
 
 
+ROW_EDGE_NNZ = (1, 63, 64, 65, 127, 128, 129, 400)
+
+
+def row_edge_csr(V, seed=0, n_filler=150):
+    """The corpus for kernels that take a row per wave, 64 non-zeros at a time: returns
+    (csr, {edge name: document id}).  ``n_filler`` rows of ``random_csr`` (1 to 40 non-zeros)
+    and, spread among them,
+
+    * ``empty_first`` / ``empty_mid`` / ``empty_last``: documents 0, n // 2 and n - 1 are empty;
+    * ``nnz1`` ... ``nnz400``: rows of exactly 1, 63, 64, 65, 127, 128, 129 and 400 non-zeros
+      (the 64-entry blocks: one short of full, full, one over; twice), so V > 400;
+    * ``col0`` / ``col_last``: a single non-zero at column 0 / V - 1;
+    * ``count1000``: a filler row with one count of 1000.
+    The number of documents is a multiple of neither 8 nor 64.  Every property is asserted
+    here, so no seed is searched."""
+    assert V > max(ROW_EDGE_NNZ)
+    rng = np.random.default_rng(seed + 1)
+    names = ["nnz%d" % k for k in ROW_EDGE_NNZ] + ["col0", "col_last"]
+    n = n_filler + len(names) + 3
+    while n % 8 == 0 or n % 64 == 0:
+        n += 1
+    x = random_csr(n, V, 40, seed=seed).toarray()
+    marks = {"empty_first": 0, "empty_mid": n // 2, "empty_last": n - 1}
+    step = (n - 2) // (len(names) + 1)
+    spots = [5 + i * step for i in range(len(names) + 1)]
+    spots = [d + 1 if d in marks.values() else d for d in spots]
+    for d in marks.values():
+        x[d] = 0
+    for name, d in zip(names, spots):
+        marks[name] = d
+        x[d] = 0
+        if name == "col0":
+            x[d, 0] = 2
+        elif name == "col_last":
+            x[d, V - 1] = 3
+        else:
+            k = int(name[3:])
+            x[d, rng.choice(V, size=k, replace=False)] = rng.integers(1, 5, size=k)
+    marks["count1000"] = spots[-1]
+    x[spots[-1], np.flatnonzero(x[spots[-1]])[0]] = 1000
+    m = sp.csr_matrix(x, dtype=np.float32)
+    m.sort_indices()
+    # ---- every property, checked
+    nnz = np.diff(m.indptr)
+    assert len(set(marks.values())) == len(marks) == len(names) + 4
+    assert n % 8 and n % 64 and m.shape == (n, V) and m.has_sorted_indices
+    assert marks["empty_first"] == 0 and marks["empty_last"] == n - 1
+    assert all(nnz[marks[k]] == 0 for k in ("empty_first", "empty_mid", "empty_last"))
+    assert all(nnz[marks["nnz%d" % k]] == k for k in ROW_EDGE_NNZ)
+    for name, col in (("col0", 0), ("col_last", V - 1)):
+        r = m[marks[name]]
+        assert r.nnz == 1 and int(r.indices[0]) == col
+    r = m[marks["count1000"]]
+    assert 1 <= r.nnz <= 40 and float(r.data.max()) == 1000.0 and int((m.data == 1000).sum()) == 1
+    filler = np.setdiff1d(np.arange(n), list(marks.values()))
+    assert len(filler) >= n_filler - 1 and nnz[filler].min() >= 1 and nnz[filler].max() <= 40
+    assert (m.data > 0).all() and (m.data == np.floor(m.data)).all()
+    return m, marks
+
+
 def edge_csr(n_docs, V, nnz_per_row, plan, s_partial, seed=0, tile=64):
     """``random_csr`` with the rows a kernel can go wrong on, placed by the batch plan (so
     no seed search): returns (csr, {edge name: document id}).

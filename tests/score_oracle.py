@@ -1,17 +1,12 @@
 """float64 numpy oracle of held-out scoring, written out from a model's ``state_dict``
 (shared by tests/test_score.py and tests/test_score_gpu.py; not a test module).
 
-Eval mode throughout: batch-norm with running statistics, no dropout, softplus MLP.
+Eval mode throughout: batch-norm with running statistics, no dropout; the encoder is the
+oracle of tests/infer_oracle.py (every activation, any depth, CTM and label inputs).
 """
 import numpy as np
 
-
-def np_state(tm):
-    return {k: v.detach().double().cpu().numpy() for k, v in tm.model.state_dict().items()}
-
-
-def _softplus(z):
-    return np.logaddexp(0.0, z)
+from tests.infer_oracle import np_state, oracle_moments  # noqa: F401  (re-exported)
 
 
 def _softmax(z):
@@ -23,33 +18,6 @@ def _softmax(z):
 def _logsumexp(z):
     m = z.max(-1, keepdims=True)
     return m + np.log(np.exp(z - m).sum(-1, keepdims=True))
-
-
-def oracle_moments(tm, X, ctx=None, labels=None):
-    """(mu, log sigma^2) [D, K] of the eval-mode encoder (softplus activation only)."""
-    assert tm.activation == "softplus"
-    sd = np_state(tm)
-    bn_eps = tm.model.inf_net.f_mu_batchnorm.eps
-    x = np.asarray(X.toarray(), dtype=np.float64)
-    if tm.kind == "ctm":
-        c = np.asarray(ctx, dtype=np.float64)
-        if tm.inference_type == "combined":
-            parts = [x, c @ sd["inf_net.adapt_bert.weight"].T + sd["inf_net.adapt_bert.bias"]]
-        else:
-            parts = [c]
-        if labels is not None:
-            parts.append(np.asarray(labels, dtype=np.float64))
-        x = np.concatenate(parts, 1)
-    h = _softplus(x @ sd["inf_net.input_layer.weight"].T + sd["inf_net.input_layer.bias"])
-    for l in range(len(tm.hidden_sizes) - 1):
-        h = _softplus(h @ sd[f"inf_net.hiddens.l_{l}.0.weight"].T + sd[f"inf_net.hiddens.l_{l}.0.bias"])
-
-    def head(name):
-        z = h @ sd[f"inf_net.{name}.weight"].T + sd[f"inf_net.{name}.bias"]
-        return (z - sd[f"inf_net.{name}_batchnorm.running_mean"]) / np.sqrt(
-            sd[f"inf_net.{name}_batchnorm.running_var"] + bn_eps)
-
-    return head("f_mu"), head("f_sigma")
 
 
 def oracle_score(tm, X, eps=None, ctx=None, labels=None):

@@ -15,48 +15,9 @@ from gfedntm_amd.data.bow import BatchPlan, BOWDataset, DeviceCSR
 from gfedntm_amd.eval.export import postprocess_thetas
 from gfedntm_amd.models import AVITM, CombinedTM, ZeroShotTM
 from tests.helpers import random_csr
+from tests.infer_oracle import infer_normals, philox4x32_10  # noqa: F401  (imported from here too)
 
 pytestmark = pytest.mark.gpu
-
-U32 = np.uint64(0xFFFFFFFF)
-
-
-def philox4x32_10(seed: int, c0, c1, c2, c3):
-    """csrc/gfk_common.h philox(): 10 rounds, key (seed lo, seed hi)."""
-    k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64((seed >> 32) & 0xFFFFFFFF)
-    shape = np.broadcast(np.asarray(c0), np.asarray(c1), np.asarray(c2), np.asarray(c3)).shape
-    x = [np.broadcast_to(np.asarray(v, dtype=np.uint64), shape).copy() for v in (c0, c1, c2, c3)]
-    for _ in range(10):
-        p0 = np.uint64(0xD2511F53) * x[0]
-        p1 = np.uint64(0xCD9E8D57) * x[2]
-        x = [((p1 >> np.uint64(32)) ^ x[1] ^ k0) & U32, p1 & U32,
-             ((p0 >> np.uint64(32)) ^ x[3] ^ k1) & U32, p0 & U32]
-        k0 = (k0 + np.uint64(0x9E3779B9)) & U32
-        k1 = (k1 + np.uint64(0xBB67AE85)) & U32
-    return x
-
-
-def infer_normals(seed: int, n_docs: int, K: int, S: int) -> np.ndarray:
-    """[S, n_docs, K] draws of csrc/infer.hip: Philox(idx = d K + k, ctr = s / 4,
-    tag RNG_INFER = 4), Box-Muller on both halves."""
-    idx = (np.arange(n_docs, dtype=np.uint64)[:, None] * np.uint64(K)
-           + np.arange(K, dtype=np.uint64)[None, :])
-    out = np.empty((S, n_docs, K))
-    for c in range((S + 3) // 4):
-        r = philox4x32_10(seed, idx, c, 4, 0x5EED)
-        f = [v.astype(np.float64) for v in r]
-        u1 = (np.floor(f[0] / 256) + 1) / 2**24
-        u2 = np.floor(f[1] / 256) / 2**24
-        u3 = (np.floor(f[2] / 256) + 1) / 2**24
-        u4 = np.floor(f[3] / 256) / 2**24
-        ra, rb = np.sqrt(-2 * np.log(u1)), np.sqrt(-2 * np.log(u3))
-        n4 = (ra * np.cos(2 * np.pi * u2), ra * np.sin(2 * np.pi * u2),
-              rb * np.cos(2 * np.pi * u4), rb * np.sin(2 * np.pi * u4))
-        for j in range(4):
-            if 4 * c + j < S:
-                out[4 * c + j] = n4[j]
-    return out
-
 
 def _trained(K=20, H=(32, 24), V=700, n_docs=300, steps=5, seed=0, model_type="prodLDA",
              activation="softplus"):
@@ -117,7 +78,7 @@ def test_postprocess_chunking_and_api():
     tm, X, data = _trained()
     e = tm.engine
     th = e.theta_infer(data, n_samples=20, seed=5)
-    th_small = e.theta_infer(data, n_samples=20, seed=5, chunk=37)     # other grid + chunks
+    th_small = e.theta_infer(data, n_samples=20, seed=5, chunk=37)     # 9 launches, doc0 != 0
     assert torch.equal(th, th_small)
     thr = float(np.float32(3e-3))
     pp = e.theta_infer(data, n_samples=20, seed=5, postprocess=True, threshold=thr)

@@ -53,7 +53,8 @@ def test_split_equals_oracle(rate):
     hk, hr = thin.split(X, rate, SPLIT_SEED, engine="host")       # fused == host, exactly
     assert_same_csr(_host(kept), hk)
     assert_same_csr(_host(rest), hr)
-    for other in (thin.split(data, rate, SPLIT_SEED, chunk=37),   # other chunks and grids
+    # chunk=37: two launches, doc0 = 37 (grids smaller than the work: tests/test_eval_grid_gpu.py)
+    for other in (thin.split(data, rate, SPLIT_SEED, chunk=37),
                   thin.split(X, rate, SPLIT_SEED, engine="fused")):
         _same_device_csr(other[0], kept)
         _same_device_csr(other[1], rest)
