@@ -1,7 +1,9 @@
 """Topic-model quality metrics.
 
 * TSS / DSS on synthetic ground truth -- reference experiments/dss_tss/run_simulation.py:321-355
-  and federated_avitm.py:152-193.
+  and federated_avitm.py:152-193.  numpy on the host by default; ``engine="device"`` (and
+  CUDA tensor inputs) take both in float64 on the matrix cores from 64 x 64 tiles, with no
+  [D, D] matrix (csrc/simscore.hip, ops/simscore.py).
 * NPMI coherence -- the reference delegates to the (missing) topicmodeler/gensim
   ``c_npmi`` (tm_wrapper.py:358-384).  Defined here precisely: for the top-N
   words of each topic, the mean over unordered word pairs of
@@ -25,15 +27,83 @@ import scipy.sparse as sp
 import torch
 
 
-def tss(betas: np.ndarray, topic_vectors: np.ndarray) -> float:
+def _sim_engine(engine: Optional[str], *operands) -> str:
+    """"host" or "device" for the similarity scores: None follows the operands (CUDA tensors
+    -> the kernels of csrc/simscore.hip, anything else -> numpy)."""
+    if engine not in (None, "host", "device"):
+        raise ValueError("engine must be None, 'host' or 'device'")
+    if engine is None:
+        engine = "device" if any(torch.is_tensor(o) and o.is_cuda for o in operands) else "host"
+    if engine == "device" and not torch.cuda.is_available():
+        raise RuntimeError("engine='device' needs a GPU")
+    return engine
+
+
+def _sim_operands(engine: str, *operands):
+    """The operands as numpy arrays (host) or fp32 / fp64 CUDA tensors (device: numpy inputs
+    are uploaded, onto the device of the first CUDA operand if there is one)."""
+    operands = [o if torch.is_tensor(o) else np.asarray(o) for o in operands]
+    for o in operands:
+        if len(o.shape) != 2:
+            raise ValueError(f"expected 2-D operands, got shape {tuple(o.shape)}")
+    if engine == "host":
+        return [o.detach().cpu().numpy() if torch.is_tensor(o) else o for o in operands]
+    dev = next((o.device for o in operands if torch.is_tensor(o) and o.is_cuda),
+               torch.device("cuda", torch.cuda.current_device()))
+    out = []
+    for o in operands:
+        t = o.detach() if torch.is_tensor(o) else torch.tensor(o)
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.double()
+        out.append(t.to(dev))
+    return out
+
+
+def bhattacharyya(x, y, engine: Optional[str] = None):
+    """Bhattacharyya coefficients ``BC[i][j] = sum_l sqrt(x[i][l] y[j][l])`` of the rows of
+    ``x`` [M, L] and ``y`` [N, L] in float64: a numpy array on the host, a tensor on the
+    operands' device from the kernels (``engine`` as for :func:`tss`)."""
+    engine = _sim_engine(engine, x, y)
+    x, y = _sim_operands(engine, x, y)
+    if x.shape[1] != y.shape[1]:
+        raise ValueError(f"rows of {x.shape[1]} and {y.shape[1]} entries cannot be compared")
+    if engine == "device":
+        from ..ops import simscore
+        return simscore.bhattacharyya(x, y)
+    return np.sqrt(np.asarray(x, dtype=np.float64)).dot(np.sqrt(np.asarray(y, dtype=np.float64)).T)
+
+
+def tss(betas, topic_vectors, engine: Optional[str] = None) -> float:
     """Topic similarity score: sum over ground-truth topics of the best Bhattacharyya
-    coefficient with a learned topic (run_simulation.py:321-334)."""
+    coefficient with a learned topic (run_simulation.py:321-334).
+
+    ``engine``: "host" -- the numpy product, in the dtype of the inputs; "device" -- the
+    float64 matrix-core kernels of csrc/simscore.hip whatever the inputs' dtype (numpy inputs
+    are uploaded; raises without a GPU or the kernel library); None -- device for CUDA
+    tensors, host otherwise."""
+    engine = _sim_engine(engine, betas, topic_vectors)
+    betas, topic_vectors = _sim_operands(engine, betas, topic_vectors)
+    if betas.shape[1] != topic_vectors.shape[1]:
+        raise ValueError(f"topics over {betas.shape[1]} and {topic_vectors.shape[1]} words "
+                         "cannot be compared")
+    if engine == "device":
+        from ..ops import simscore
+        return float(simscore.tss(betas, topic_vectors).item())
     return float(np.sum(np.max(np.sqrt(betas).dot(np.sqrt(topic_vectors.T)), axis=0)))
 
 
-def dss(thetas_true: np.ndarray, thetas: np.ndarray, n_docs: Optional[int] = None) -> float:
-    """Document similarity score (run_simulation.py:337-355)."""
+def dss(thetas_true, thetas, n_docs: Optional[int] = None, engine: Optional[str] = None) -> float:
+    """Document similarity score (run_simulation.py:337-355).  ``engine`` as for :func:`tss`;
+    the host formula builds two dense [D, D] matrices, the device path 64 x 64 tiles of them."""
+    engine = _sim_engine(engine, thetas_true, thetas)
+    thetas_true, thetas = _sim_operands(engine, thetas_true, thetas)
+    if thetas_true.shape[0] != thetas.shape[0]:
+        raise ValueError(f"thetas_true has {thetas_true.shape[0]} documents, thetas "
+                         f"{thetas.shape[0]}")
     n_docs = len(thetas_true) if n_docs is None else n_docs
+    if engine == "device":
+        from ..ops import simscore
+        return float(simscore.dss(thetas_true, thetas, n_docs).item())
     a = np.sqrt(thetas_true).dot(np.sqrt(thetas_true.T))
     b = np.sqrt(thetas).dot(np.sqrt(thetas.T))
     return float(np.sum(np.abs(a - b)) / n_docs)

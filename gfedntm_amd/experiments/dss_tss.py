@@ -35,6 +35,8 @@ absolute difference of the documents' Bhattacharyya similarity matrices, true
 vs inferred.  ``experiment`` 0 sweeps ``frozen_topics_list``, 1 sweeps
 ``eta_list`` (the topic Dirichlet parameter beta).  Results: ``results.json`` and
 ``results.csv`` (mean / std over ``iters``) instead of a pickled DataFrame.
+``metrics_engine``: "host" (default) takes a trained model's TSS and DSS with numpy in the
+dtype of the thetas, "device" with the float64 kernels of csrc/simscore.hip.
 
 Usage: ``python -m gfedntm_amd.experiments.dss_tss --config cfg.json --out results/``
 """
@@ -63,7 +65,9 @@ DEFAULTS = dict(n_nodes=5, vocab_size=5000, n_topics=50, beta=1e-2, alpha=0.1, n
                 hidden_sizes=[100, 100], num_epochs=100, batch_size=64, lr=2e-3,
                 # new
                 federated=True, device=None, backend="auto", seed=0, arms=None,
-                reference_tss=True)
+                reference_tss=True,
+                # "host": numpy TSS / DSS; "device": the float64 kernels of csrc/simscore.hip
+                metrics_engine="host")
 
 ARMS = ("centralized", "non_colab", "baseline", "federated", "federated_matched",
         "federated_grads", "federated_bf16delta")
@@ -136,9 +140,11 @@ def _reference_reindex(wd: np.ndarray, id2token: Dict[int, str], vocab_size: int
 
 
 def _score(tm, id2token, vocab, cfg, inf_counts, topic_vectors, inf_thetas):
+    engine = cfg.get("metrics_engine", "host")
     wd = tm.get_topic_word_distribution()                  # softmax(beta)
     # the TSS of the learned topic-word distribution on the right columns ...
-    true_tss = tss(betas_to_ground_truth_vocab(wd, id2token, cfg["vocab_size"]), topic_vectors)
+    true_tss = tss(betas_to_ground_truth_vocab(wd, id2token, cfg["vocab_size"]), topic_vectors,
+                   engine=engine)
     if cfg.get("reference_tss", True):
         # ... and the number the reference simulator would print for the same model
         wd = _softmax_rows(_softmax_rows(wd))              # run_simulation.py:417 + :257
@@ -147,7 +153,8 @@ def _score(tm, id2token, vocab, cfg, inf_counts, topic_vectors, inf_thetas):
         betas = betas_to_ground_truth_vocab(wd, id2token, cfg["vocab_size"])
     thetas = np.asarray(tm.get_doc_topic_distribution(BOWDataset(_remap(inf_counts, vocab),
                                                                  id2token)))
-    return tss(betas, topic_vectors), dss(inf_thetas, thetas), true_tss
+    return (tss(betas, topic_vectors, engine=engine), dss(inf_thetas, thetas, engine=engine),
+            true_tss)
 
 
 def run_iteration(cfg, frozen_topics: int, eta: float, device, seed: int) -> Dict[str, tuple]:

@@ -523,10 +523,83 @@ class TopicModelBase:
         """softmax over V of the topic-word matrix (reference avitm.py:539-551).  For
         NeuralLDA the reference softmaxes an already-normalised matrix (B9); that is kept
         when ``compat_double_softmax`` is True."""
+        return self._topic_word_distribution_tensor().cpu().numpy()
+
+    @torch.no_grad()
+    def _topic_word_distribution_tensor(self) -> torch.Tensor:
+        """:meth:`get_topic_word_distribution` as a tensor on the model's device."""
         m = self.topic_word_matrix_tensor()
         if not self.model.is_prodlda and not self.compat_double_softmax:
-            return m.cpu().numpy()
-        return torch.softmax(m.double(), dim=1).cpu().numpy()
+            return m
+        return torch.softmax(m.double(), dim=1)
+
+    # ---------------------------------------------------------------- synthetic ground truth
+    @torch.no_grad()
+    def dss(self, dataset, thetas_true, n_samples: int = 20, seed: Optional[int] = None,
+            postprocess: bool = False) -> float:
+        """Document similarity score of the model's thetas of ``dataset`` against the
+        generator's ``thetas_true`` [D, K_true] (eval/metrics.py dss).  ``postprocess``: the
+        theta threshold + L1 normalisation first (eval/export.py postprocess_thetas).
+
+        Fused backend: the thetas of ``engine.theta_infer`` (its fused post-processing
+        included) go straight into the float64 tile kernels of csrc/simscore.hip; neither
+        they nor a [D, D] matrix exist on the host, only the scalar is read back.  Other
+        backends: the host formula on float64 casts of :meth:`get_doc_topic_distribution`."""
+        from ..eval import metrics
+        if seed is None:
+            seed = int(torch.initial_seed()) % (2**31)
+        if len(thetas_true) != len(dataset):
+            raise ValueError(f"thetas_true has {len(thetas_true)} documents, the dataset "
+                             f"{len(dataset)}")
+        if self.backend == "fused":
+            th = self.engine.theta_infer(self.device_data(dataset), n_samples, seed=seed,
+                                         postprocess=postprocess)
+            return metrics.dss(thetas_true, th, engine="device")
+        th = np.asarray(self.get_doc_topic_distribution(dataset, n_samples, seed=seed),
+                        dtype=np.float64)
+        if postprocess:
+            from ..eval.export import postprocess_thetas
+            th = postprocess_thetas(th)
+        tt = thetas_true.detach().cpu().numpy() if torch.is_tensor(thetas_true) else thetas_true
+        return metrics.dss(np.asarray(tt, dtype=np.float64), th, engine="host")
+
+    @torch.no_grad()
+    def tss(self, topic_vectors, columns=None) -> float:
+        """Topic similarity score of softmax(beta) (:meth:`get_topic_word_distribution`)
+        against the generator's ``topic_vectors`` [K_true, V_true] (eval/metrics.py tss).
+        ``columns``: for each learned vocabulary column its generator column (the map of
+        eval/metrics.py betas_to_ground_truth_vocab); the learned rows are scattered onto the
+        generator vocabulary, zero elsewhere, and L1-normalised in float64.  Without it the
+        two vocabularies must be the same.
+
+        Fused backend: scatter, normalisation and the float64 kernels of csrc/simscore.hip on
+        the device, from the model's beta without a host round trip.  Other backends: numpy
+        on float64 casts."""
+        from ..eval import metrics
+        wd = self._topic_word_distribution_tensor().double()
+        tv = topic_vectors if torch.is_tensor(topic_vectors) else \
+            torch.from_numpy(np.ascontiguousarray(topic_vectors))
+        if tv.dim() != 2:
+            raise ValueError("topic_vectors must be [topics, vocabulary]")
+        if columns is not None:
+            cols = torch.as_tensor(np.asarray(columns, dtype=np.int64) if not
+                                   torch.is_tensor(columns) else columns).long().reshape(-1)
+            if int(cols.numel()) != wd.shape[1]:
+                raise ValueError(f"columns maps {int(cols.numel())} words, the model has "
+                                 f"{wd.shape[1]}")
+            if cols.numel() and (int(cols.min()) < 0 or int(cols.max()) >= tv.shape[1]):
+                raise ValueError(f"columns must lie in [0, {tv.shape[1]})")
+            out = torch.zeros(wd.shape[0], tv.shape[1], dtype=torch.float64, device=wd.device)
+            out[:, cols.to(wd.device)] = wd
+            s = out.sum(dim=1, keepdim=True)
+            s[s == 0] = 1.0
+            wd = out / s
+        elif wd.shape[1] != tv.shape[1]:
+            raise ValueError(f"the model has {wd.shape[1]} words, topic_vectors {tv.shape[1]}: "
+                             "pass columns")
+        if self.backend == "fused":
+            return metrics.tss(wd, tv.to(wd.device), engine="device")
+        return metrics.tss(wd.cpu().numpy(), tv.detach().double().cpu().numpy(), engine="host")
 
     def get_topics(self, k=10):
         if k > self.input_size:

@@ -191,6 +191,23 @@ class GfkCooc(C.Structure):
                 ("W", C.c_int32), ("V", C.c_int32), ("max_grid", C.c_int32)]
 
 
+class GfkDss(C.Structure):
+    """document similarity score launch (csrc/simscore.hip)."""
+    _fields_ = [("a", P), ("b", P), ("part", P), ("out", P),
+                ("lda", C.c_int64), ("ldb", C.c_int64), ("n_docs", C.c_int64),
+                ("part_len", C.c_int64),
+                ("D", C.c_int32), ("Ka", C.c_int32), ("Kb", C.c_int32),
+                ("a_f64", C.c_int32), ("b_f64", C.c_int32), ("max_grid", C.c_int32)]
+
+
+class GfkBc(C.Structure):
+    """Bhattacharyya matrix / topic similarity score launch (csrc/simscore.hip)."""
+    _fields_ = [("x", P), ("y", P), ("part", P), ("bc", P), ("tss", P),
+                ("ldx", C.c_int64), ("ldy", C.c_int64), ("part_len", C.c_int64),
+                ("M", C.c_int32), ("N", C.c_int32), ("L", C.c_int32),
+                ("x_f64", C.c_int32), ("y_f64", C.c_int32), ("max_grid", C.c_int32)]
+
+
 class GfkThin(C.Structure):
     """token-wise thinning launch (csrc/thin.hip)."""
     _fields_ = [("indptr", P), ("indices", P), ("values", P), ("theta", P), ("tw", P),
@@ -282,6 +299,22 @@ def declare(lib: C.CDLL) -> None:
     lib.gfk_cooc.restype = C.c_int
     lib.gfk_cooc_max_words.argtypes = []
     lib.gfk_cooc_max_words.restype = C.c_int
+    lib.gfk_dss_struct_size.restype = C.c_size_t
+    lib.gfk_bc_struct_size.restype = C.c_size_t
+    if lib.gfk_dss_struct_size() != C.sizeof(GfkDss):
+        raise RuntimeError("GfkDss ABI mismatch")
+    if lib.gfk_bc_struct_size() != C.sizeof(GfkBc):
+        raise RuntimeError("GfkBc ABI mismatch")
+    lib.gfk_dss.argtypes = [C.POINTER(GfkDss), C.c_void_p]
+    lib.gfk_dss.restype = C.c_int
+    lib.gfk_bc.argtypes = [C.POINTER(GfkBc), C.c_void_p]
+    lib.gfk_bc.restype = C.c_int
+    lib.gfk_sim_max_rows.argtypes = []
+    lib.gfk_sim_max_rows.restype = C.c_int
+    lib.gfk_dss_items.argtypes = [C.c_int64]
+    lib.gfk_dss_items.restype = C.c_int64
+    lib.gfk_bc_ranges.argtypes = [C.c_int]
+    lib.gfk_bc_ranges.restype = C.c_int
     lib.gfk_thin_struct_size.restype = C.c_size_t
     if lib.gfk_thin_struct_size() != C.sizeof(GfkThin):
         raise RuntimeError("GfkThin ABI mismatch")

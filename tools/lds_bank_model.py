@@ -143,6 +143,20 @@ def winctx_accesses(H0: int, B: int = 64, stride_a: int = 64, stride_z: Optional
              lambda w, l: 4 * ((l >> 4) * sz + (w // 4) * 16 + (l & 15)), B // 4)]
 
 
+# ---------------------------------------------------------------------------------------
+# csrc/simscore.hip ss_tile: f64 rows [64][ld], MFMA operand X[lane & 15][k + (lane >> 4)]
+def simscore_accesses(ld: int = 18, kc: int = 16) -> List[Access]:
+    A: List[Access] = []
+    A.append(("stage store (b64)", "ds_write_b64",
+              lambda w, l: 8 * (((64 * w + l) // kc) * ld + (64 * w + l) % kc), 2 * 64 * kc // 256))
+    for m in range(2):
+        A.append((f"A role m={m} (b64)", "ds_read_b64",
+                  lambda w, l, m=m: 8 * ((32 * (w >> 1) + 16 * m + (l & 15)) * ld + (l >> 4)), kc // 4))
+        A.append((f"B role n={m} (b64)", "ds_read_b64",
+                  lambda w, l, m=m: 8 * ((32 * (w & 1) + 16 * m + (l & 15)) * ld + (l >> 4)), kc // 4))
+    return A
+
+
 def table(rows: List[dict]) -> str:
     out = ["| kernel | access group | instruction | per tile | LDS cycles | conflict cycles |",
            "|---|---|---|---|---|---|"]
@@ -173,6 +187,9 @@ def main():
     rows += run("post colstats K=100, rows at 114", post_accesses(100, ld=114), 16)
     rows += run("win_tile_ctx H0=50, strides 64 / 50", winctx_accesses(50), 8)
     rows += run("win_tile_ctx H0=50, strides 80 / 80", winctx_accesses(50, stride_a=80, stride_z=80), 8)
+    rows += run("simscore ss_tile, row stride 18 doubles", simscore_accesses(18), 4)
+    rows += run("simscore ss_tile, row stride 16 doubles", simscore_accesses(16), 4)
+    rows += run("simscore ss_tile, row stride 17 doubles", simscore_accesses(17), 4)
     md = table(rows)
     print(md)
     if a.md:
