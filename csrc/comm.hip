@@ -357,6 +357,14 @@ extern "C" __global__ void __launch_bounds__(CT) gfk_xgmi_allreduce_bf16d(GfkCom
 //   0  the sum is written back to every client's buffer (LocalFederation round);
 //   1  the sum is written to f_0 only (a rank's local partial, before the collective);
 //   2  broadcast: f_0 is copied into f_1 .. f_{n-1} (after the collective).
+// Batched clients that READ one shared copy S of the shared prefix (GfkModel.off_own) and
+// write their own buffers take three more, with S = dst:
+//   3  the sum is written to S only (a round no host looks behind: M reads, 1 write);
+//   4  the sum is written to S and to every client's buffer (the last round of a replay);
+//   5  refresh: f_0 is copied into S (before the first round after the host touched f).
+// Up to FV clients in one group take gfk_local_fedavg_v for these: the buffer pointers come
+// by value in the kernel arguments (no table load ahead of the data loads) and a thread
+// owns ONE float4, so all of its loads are in flight before its first add.
 // One launch replaces the 2N + 1 eager kernels of a zero / add / copy sequence and is
 // captured into the round graphs.  The client buffers and the group ends come from small
 // DEVICE tables (uploaded once per client set, before any capture), so the number of
@@ -374,6 +382,7 @@ struct GfkLocalAvg {
   int32_t mode;
   int32_t n_groups;
   int32_t pad;
+  float* dst;                    // modes 3 - 5: the shared read copy S (else unused)
 };
 
 namespace {
@@ -429,16 +438,56 @@ extern "C" __global__ void __launch_bounds__(256) gfk_local_fedavg(GfkLocalAvg a
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const int64_t n4 = a.n >> 2;
   const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int w1 = a.mode == 1 ? 1 : a.n_clients;     // buffers written
+  const bool copy = a.mode == 2 || a.mode == 5;     // f_0 as it is, no sum
+  const int w1 = a.mode == 1 ? 1 : a.mode == 3 || a.mode == 5 ? 0 : a.n_clients;   // buffers written
   const int w0 = a.mode == 2 ? 1 : 0;
+  float* dst = a.mode >= 3 ? a.dst + a.off : nullptr;
   for (int64_t i = g; i < n4; i += stride) {
-    const float4 acc = a.mode == 2 ? lptr<const float4>(a, 0)[i] : fold_regs(a, i);
+    const float4 acc = copy ? lptr<const float4>(a, 0)[i] : fold_regs(a, i);
     for (int j = w0; j < w1; ++j) lptr<float4>(a, j)[i] = acc;
+    if (dst) reinterpret_cast<float4*>(dst)[i] = acc;
   }
   if (g < (a.n & 3)) {           // the partial float4 at the end: nothing past n is touched
     const int64_t i = (n4 << 2) + g;
-    const float acc = a.mode == 2 ? lptr<const float>(a, 0)[i] : fold<float>(a, i);
+    const float acc = copy ? lptr<const float>(a, 0)[i] : fold<float>(a, i);
     for (int j = w0; j < w1; ++j) lptr<float>(a, j)[i] = acc;
+    if (dst) dst[i] = acc;
+  }
+}
+
+// Modes 3 - 5 for up to FV clients in one group: the client-order left fold of fold_regs with
+// one group (the same bits), one float4 per thread, the pointers in the kernel arguments.
+struct GfkLocalAvgV {
+  float* f[FV];                  // the clients' buffers (entries past n_clients unused)
+  float* dst;                    // S
+  int64_t off, n;                // the folded float range, as GfkLocalAvg's
+  int32_t n_clients, mode;
+};
+
+extern "C" __global__ void __launch_bounds__(256) gfk_local_fedavg_v(GfkLocalAvgV a) {
+  const int64_t n4 = a.n >> 2;
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int ns = a.mode == 5 ? 1 : a.n_clients;     // buffers read
+  const int nw = a.mode == 4 ? a.n_clients : 0;     // client buffers written
+  if (g < n4) {
+    float4 v[FV];
+#pragma unroll
+    for (int j = 0; j < FV; ++j) v[j] = reinterpret_cast<const float4*>(a.f[j < ns ? j : 0] + a.off)[g];
+    float4 acc = v[0];
+#pragma unroll
+    for (int j = 1; j < FV; ++j)
+      if (j < ns) acc = acc + v[j];
+    reinterpret_cast<float4*>(a.dst + a.off)[g] = acc;
+#pragma unroll
+    for (int j = 0; j < FV; ++j)
+      if (j < nw) reinterpret_cast<float4*>(a.f[j] + a.off)[g] = acc;
+  }
+  if (g < (a.n & 3)) {           // the partial float4 at the end: nothing past n is touched
+    const int64_t i = a.off + (n4 << 2) + g;
+    float acc = a.f[0][i];
+    for (int j = 1; j < ns; ++j) acc += a.f[j][i];
+    a.dst[i] = acc;
+    for (int j = 0; j < nw; ++j) a.f[j][i] = acc;
   }
 }
 
@@ -447,10 +496,27 @@ extern "C" size_t gfk_local_avg_struct_size() { return sizeof(GfkLocalAvg); }
 // the tables' contents (client count, group ends, pointer alignment) are checked by the
 // caller when it builds them (parallel/aggregator.py _LocalTable)
 extern "C" int gfk_local_fedavg_launch(const GfkLocalAvg* a, int grid, hipStream_t s) {
-  if (a->n_clients < 1 || grid < 1 || a->mode < 0 || a->mode > 2 || a->n_groups < 1 ||
+  if (a->n_clients < 1 || grid < 1 || a->mode < 0 || a->mode > 5 || a->n_groups < 1 ||
       a->n_groups > a->n_clients || !a->f || !a->gend || (a->off & 3) || a->off < 0 || a->n < 0)
     return -1;
+  if (a->mode >= 3 && (!a->dst || ((uintptr_t)a->dst & 15))) return -1;
   hipLaunchKernelGGL(gfk_local_fedavg, dim3(grid), dim3(256), 0, s, *a);
+  return (int)hipGetLastError();
+}
+
+extern "C" size_t gfk_local_avg_v_struct_size() { return sizeof(GfkLocalAvgV); }
+
+// (the grid is the range's float4s, one per thread; the caller checks the buffers' lengths)
+extern "C" int gfk_local_fedavg_v_launch(const GfkLocalAvgV* a, hipStream_t s) {
+  if (a->n_clients < 1 || a->n_clients > FV || a->mode < 3 || a->mode > 5 || (a->off & 3) ||
+      a->off < 0 || a->n < 0 || !a->dst || ((uintptr_t)a->dst & 15))
+    return -1;
+  for (int j = 0; j < a->n_clients; ++j)
+    if (!a->f[j] || ((uintptr_t)a->f[j] & 15)) return -1;
+  const int64_t n4 = a->n >> 2;
+  const int64_t grid = n4 > 0 ? (n4 + 255) / 256 : 1;
+  if (grid > 0x7FFFFFFF) return -1;
+  hipLaunchKernelGGL(gfk_local_fedavg_v, dim3((unsigned)grid), dim3(256), 0, s, *a);
   return (int)hipGetLastError();
 }
 

@@ -186,6 +186,14 @@ typedef struct GfkModel {
   // SURVEY 5.5): written next to loss_hist by the batch-level workgroup when non-null ----
   float* kl_hist;
   float* rl_hist;
+  // ---- batched clients reading ONE shared copy of the shared prefix (ops/engine.py
+  // BatchedSteps.set_shared_reads): every pointer into the shared prefix, flat_base included,
+  // addresses the shared copy S, which the kernels only read; the client's own buffer is
+  // own = p + off_own (floats), where the new parameter / running statistic is stored.
+  // off_m / off_v / off_g of such a descriptor are taken from p as well (the host adds
+  // off_own), so the Adam moments and the gradient slot stay the client's.  0: p is the
+  // client's own buffer.  Read by the batched (GB) instances only: gfk_own
+  int64_t off_own;
 } GfkModel;
 
 // stage_flags bit 16 (GFK_FWD_POSTFOLD): the ProdLDA strip forward's ring variant computes
@@ -663,6 +671,13 @@ __device__ __forceinline__ void param_update(const GfkModel& m, float* ptr, floa
 
 __device__ __forceinline__ bool is_shared(const GfkModel& m, const float* ptr) {
   return (ptr - m.flat_base) < m.n_shared;
+}
+// Where a kernel stores the new value of a shared tensor it read at p: p[gfk_own<GB>(m)].
+// A constant 0 in the one-client instances (their code does not change).
+template <bool GB>
+__device__ __forceinline__ int64_t gfk_own(const GfkModel& m) {
+  if constexpr (GB) return m.off_own;
+  else return 0;
 }
 template <class... T>
 __device__ __forceinline__ void keep(T&... v) { (keep1(v), ...); }

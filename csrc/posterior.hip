@@ -111,7 +111,8 @@ constexpr int NGR = FT / CG;            // row groups
 template <int RPG>
 __device__ __forceinline__ void post_colstats(const GfkModel& m, const float* mr, const float* lr,
                                               float* cmean, float* crstd, float* red, float rm0,
-                                              float rv0, int nb, float inv_nb, int row, int tid) {
+                                              float rv0, int nb, float inv_nb, int row, int tid,
+                                              int64_t own = 0) {
   constexpr int RB = 16;                  // rows per load batch (registers)
   const int K = m.K, c2 = tid % CG, grp = tid / CG;
   const int cc = min(c2, 2 * K - 1);
@@ -155,8 +156,8 @@ __device__ __forceinline__ void post_colstats(const GfkModel& m, const float* mr
       const float unb = nb > 1 ? var * (float)nb / (float)(nb - 1) : var;
       float nm = (1.f - mom) * rm0 + mom * mean, nv = (1.f - mom) * rv0 + mom * unb;
       if (m.fed_scale_on && is_shared(m, rm)) { nm *= m.fed_scale; nv *= m.fed_scale; }
-      *rm = nm;
-      *rv = nv;
+      rm[own] = nm;
+      rv[own] = nv;
       m.ws_bn_rstd[c2] = rstd;
     }
   }
@@ -169,7 +170,7 @@ template <int RPT>
 __device__ __forceinline__ void post_colstats_dpp(const GfkModel& m, const float* mr, const float* lr,
                                               float* cmean, float* crstd, const float (&rmp)[8],
                                               const float (&rvp)[8], int nb, float inv_nb, int row,
-                                              int tid, int ld) {
+                                              int tid, int ld, int64_t own = 0) {
   constexpr int CP = 8;
   const int K = m.K;
 #pragma unroll
@@ -209,8 +210,8 @@ __device__ __forceinline__ void post_colstats_dpp(const GfkModel& m, const float
         const float o_m = rmp[pass], o_v = rvp[pass];
         float nm = (1.f - mom) * o_m + mom * mean, nv = (1.f - mom) * o_v + mom * unb;
         if (m.fed_scale_on && is_shared(m, rm)) { nm *= m.fed_scale; nv *= m.fed_scale; }
-        *rm = nm;
-        *rv = nv;
+        rm[own] = nm;
+        rv[own] = nv;
         m.ws_bn_rstd[c2] = rstd;
       }
     }
@@ -389,11 +390,11 @@ __global__ void __launch_bounds__(FT) gfk_post_fwd_k(GfkArgT<GB> ga) {
       crstd[c] = m.ws_colstat[2 * K + c];
     }
   } else if constexpr (InLds) {
-    if (B <= 64) post_colstats_dpp<4>(m, mr, lr, cmean, crstd, rmp, rvp, nb, inv_nb, row, tid, LD);
-    else post_colstats_dpp<8>(m, mr, lr, cmean, crstd, rmp, rvp, nb, inv_nb, row, tid, LD);
+    if (B <= 64) post_colstats_dpp<4>(m, mr, lr, cmean, crstd, rmp, rvp, nb, inv_nb, row, tid, LD, gfk_own<GB>(m));
+    else post_colstats_dpp<8>(m, mr, lr, cmean, crstd, rmp, rvp, nb, inv_nb, row, tid, LD, gfk_own<GB>(m));
   } else {
-    if (B <= 64) post_colstats<32>(m, mr, lr, cmean, crstd, red, rm0, rv0, nb, inv_nb, row, tid);
-    else post_colstats<64>(m, mr, lr, cmean, crstd, red, rm0, rv0, nb, inv_nb, row, tid);
+    if (B <= 64) post_colstats<32>(m, mr, lr, cmean, crstd, red, rm0, rv0, nb, inv_nb, row, tid, gfk_own<GB>(m));
+    else post_colstats<64>(m, mr, lr, cmean, crstd, red, rm0, rv0, nb, inv_nb, row, tid, gfk_own<GB>(m));
   }
   if (!PS && row == 0 && tid == 0) {
     *m.nbt_mu = nbt0 + 1;

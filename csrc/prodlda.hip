@@ -261,8 +261,8 @@ __global__ void __launch_bounds__(DEC_THREADS) prodlda_fwd_kernel(GfkArgT<GB> ga
     const float unb = nb > 1 ? var * (float)nb / (float)(nb - 1) : var;
     float nm = (1.f - mom) * rm0 + mom * mean, nv = (1.f - mom) * rv0 + mom * unb;
     if (m.fed_scale_on && is_shared(m, m.beta_rm)) { nm *= m.fed_scale; nv *= m.fed_scale; }
-    m.beta_rm[v] = nm;
-    m.beta_rv[v] = nv;
+    m.beta_rm[v + gfk_own<GB>(m)] = nm;
+    m.beta_rv[v + gfk_own<GB>(m)] = nv;
     m.ws_col_rstd[v] = rstd;
   }
   GFK_STAMP(m, 19);
@@ -532,8 +532,8 @@ __global__ void __launch_bounds__(strip_threads(PF, NP)) prodlda_fwd_strip_kerne
           const float unb = nb > 1 ? var * (float)nb / (float)(nb - 1) : var;
           float nm = (1.f - mom) * rmp[p] + mom * mean, nv = (1.f - mom) * rvp[p] + mom * unb;
           if (m.fed_scale_on && is_shared(m, rmq)) { nm *= m.fed_scale; nv *= m.fed_scale; }
-          *rmq = nm;
-          *rvq = nv;
+          rmq[gfk_own<GB>(m)] = nm;
+          rvq[gfk_own<GB>(m)] = nv;
           m.ws_bn_rstd[c2] = rstd;
         }
       }
@@ -740,8 +740,8 @@ __global__ void __launch_bounds__(strip_threads(PF, NP)) prodlda_fwd_strip_kerne
       const float unb = nb > 1 ? var * (float)nb / (float)(nb - 1) : var;
       float nm = (1.f - mom) * rm0 + mom * mean, nv = (1.f - mom) * rv0 + mom * unb;
       if (m.fed_scale_on && is_shared(m, m.beta_rm)) { nm *= m.fed_scale; nv *= m.fed_scale; }
-      m.beta_rm[v] = nm;
-      m.beta_rv[v] = nv;
+      m.beta_rm[v + gfk_own<GB>(m)] = nm;
+      m.beta_rv[v + gfk_own<GB>(m)] = nv;
       m.ws_col_rstd[v] = rstd;
     }
 #ifdef GFK_STAMPS
@@ -1645,7 +1645,7 @@ __global__ void __launch_bounds__(256) prodlda_dlogit_kernel(GfkArgT<GB> ga) {
 // swizzle a per-lane constant) + bt + dt, and the dbeta tile G reuses dt's space (one
 // extra barrier): ~50 KB at B = 64, K = 200, so THREE workgroups share a CU (24 waves)
 // instead of two.
-template <int BM, int MAXU, int KQ, bool BF, bool PRE>
+template <int BM, int MAXU, int KQ, bool BF, bool PRE, bool OWN = false>
 __device__ __forceinline__ void prodlda_bwd_body(const GfkModel& m) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int NTH = KQ == 1 ? DEC_THREADS : 512;
@@ -1761,7 +1761,8 @@ __device__ __forceinline__ void prodlda_bwd_body(const GfkModel& m) {
   // per element; element rows are wave-uniform (row = kb + wave + RPU u), checked by a
   // scalar branch.  Replaces a 64-bit address + bounds branch per element.
   const int nrec = K * m.ldb * 4;               // (K ldb 4 < 0x7FFF0000: the launcher)
-  const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void*)m.beta, 0, nrec, 0x00020000);
+  // (rs_b: stores only -- the new beta goes to the client's own copy, gfk_own)
+  const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void*)(m.beta + gfk_own<OWN>(m)), 0, nrec, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_m = __builtin_amdgcn_make_buffer_rsrc((void*)(m.beta + m.off_m), 0, nrec, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc((void*)(m.beta + m.off_v), 0, nrec, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc((void*)(m.beta + m.off_g), 0, nrec, 0x00020000);
@@ -2019,7 +2020,7 @@ __device__ __forceinline__ void prodlda_bwd_body(const GfkModel& m) {
           } else {
             p[m.off_m] = mo_[u][e];
             p[m.off_v] = vo_[u][e];
-            *p = np_[u][e];
+            p[gfk_own<OWN>(m)] = np_[u][e];
           }
         }
       }
@@ -2094,7 +2095,7 @@ template <int BM, int MAXU, int KQ, bool BF, bool GB = false>
 __global__ void __launch_bounds__(KQ == 1 ? DEC_THREADS : 512, KQ == 1 ? 1 : 2)
 prodlda_bwd_kernel(GfkArgT<GB> ga) {
   const GfkModel& m = gfk_model(ga);
-  prodlda_bwd_body<BM, MAXU, KQ, BF, false>(m);
+  prodlda_bwd_body<BM, MAXU, KQ, BF, false, GB>(m);
 }
 
 // the precomputed-dlogit shape (bwd_pre = 2): the compiler's register budget, two 8-wave

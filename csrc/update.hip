@@ -73,7 +73,7 @@ extern "C" size_t gfk_win_update_smem(const GfkModel* m) {
 }
 
 // Small weight tile job (see GfkWJob).  LDS: dz[B][LDJ] + a[B][LDJ]
-template <int UT>
+template <int UT, bool GB = false>
 __device__ __forceinline__ void weight_job(const GfkModel& m, const GfkWJob& J, float* smem) {
   constexpr int UW = UT / 64;
   constexpr int LDJ = 80;            // B-role stride (16 mod 32): conflict-free operand reads
@@ -143,7 +143,7 @@ __device__ __forceinline__ void weight_job(const GfkModel& m, const GfkWJob& J, 
         if (sh && m.fed_scale_on) np *= m.fed_scale;
         p[m.off_m] = mo;
         p[m.off_v] = vo;
-        *p = np;
+        p[gfk_own<GB>(m)] = np;
       }
     }
   }
@@ -207,7 +207,7 @@ __device__ __forceinline__ void weight_job_lb(const GfkModel& m, const GfkWJob& 
 
 // Vector job (see GfkVJob): 16 lanes per element split the batch rows.  LB: the large-batch
 // instance (rows in passes of 128)
-template <int UT, bool LB = false>
+template <int UT, bool LB = false, bool GB = false>
 __device__ __forceinline__ void vector_job(const GfkModel& m, const GfkVJob& J) {
   const int tid = threadIdx.x, s = tid & 15;
   const int B = m.bmax, nb = *m.ws_nb;
@@ -246,7 +246,7 @@ __device__ __forceinline__ void vector_job(const GfkModel& m, const GfkVJob& J) 
       if (sh && m.fed_scale_on) np *= m.fed_scale;
       p[m.off_m] = pm;
       p[m.off_v] = pv;
-      *p = np;
+      p[gfk_own<GB>(m)] = np;
     }
   }
 }
@@ -269,7 +269,7 @@ constexpr int WIN_BATCH8 = 512;
 // kernel's existing LDS budget)
 // RS: row slots per thread (64 rows each): 2 up to bmax = 128, GFK_BMAX_LIMIT / 64 for the
 // large-batch plan
-template <int UT, bool VL = false, int RS = 2>
+template <int UT, bool VL = false, int RS = 2, bool GB = false>
 __device__ __forceinline__ void win_tile_sparse(const GfkModel& m, float* smem, int tile) {
   constexpr int CAP = 512;
   constexpr int TPR = UT / 64;                 // threads per row, 64 rows per pass
@@ -463,7 +463,7 @@ __device__ __forceinline__ void win_tile_sparse(const GfkModel& m, float* smem, 
     } else {
       st4(wblk + m.off_m, mo);
       st4(wblk + m.off_v, vo);
-      st4(wblk, np);
+      st4(wblk + gfk_own<GB>(m), np);
     }
   }
 }
@@ -607,8 +607,8 @@ __global__ void __launch_bounds__(UT, UT == 512 ? 8 : 1) gfk_win_update_k(GfkArg
   const int nt_here = m.n_tiles;
   {
     const int r = (int)gfk_bx() - nt_here;
-    if (r >= 0 && r < U.n_w) { weight_job<UT>(m, U.w[r], smem); return; }
-    if (r >= U.n_w && r < U.n_w + U.n_v) { vector_job<UT>(m, U.v[r - U.n_w]); return; }
+    if (r >= 0 && r < U.n_w) { weight_job<UT, GB>(m, U.w[r], smem); return; }
+    if (r >= U.n_w && r < U.n_w + U.n_v) { vector_job<UT, false, GB>(m, U.v[r - U.n_w]); return; }
     if (r == U.n_w + U.n_v) { prepare_next_batch(m, reinterpret_cast<int*>(smem)); return; }
   }
   const bool zs = m.ctx_fused == 2;            // ZeroShotTM: W_in is the dense [C, H0] layer
@@ -791,7 +791,7 @@ __global__ void __launch_bounds__(UT, UT == 512 ? 8 : 1) gfk_win_update_k(GfkArg
         if (sh && m.fed_scale_on) np *= m.fed_scale;
         p[m.off_m] = mo;
         p[m.off_v] = vo;
-        *p = np;
+        p[gfk_own<GB>(m)] = np;
       }
     }
   }
@@ -833,7 +833,7 @@ __global__ void __launch_bounds__(UT, UT == 512 ? 8 : 1) gfk_win_update_k(GfkArg
       } else {
         st4(wblk + m.off_m, mo);
         st4(wblk + m.off_v, vo);
-        st4(wblk, np);
+        st4(wblk + gfk_own<GB>(m), np);
       }
     }
   }
@@ -945,16 +945,16 @@ __global__ void __launch_bounds__(UT, VL ? 4096 / UT : 1) gfk_win_sparse_k(GfkAr
   const int r = (int)gfk_bx();
   if (r < U.n_w) {
     if constexpr (RS > 2) weight_job_lb<UT>(m, U.w[r], smem);
-    else weight_job<UT>(m, U.w[r], smem);
+    else weight_job<UT, GB>(m, U.w[r], smem);
     return;
   }
-  if (r < U.n_w + U.n_v) { vector_job<UT, (RS > 2)>(m, U.v[r - U.n_w]); return; }
+  if (r < U.n_w + U.n_v) { vector_job<UT, (RS > 2), GB>(m, U.v[r - U.n_w]); return; }
   if (r == U.n_w + U.n_v) { prepare_next_batch(m, reinterpret_cast<int*>(smem)); return; }
   const int t = r - (U.n_w + U.n_v + 1);
   if constexpr (CTX) {
     if (t >= m.n_tiles) { win_tile_ctx<UT>(m, smem, t - m.n_tiles); return; }
   }
-  win_tile_sparse<UT, VL, RS>(m, smem, t);
+  win_tile_sparse<UT, VL, RS, GB>(m, smem, t);
 }
 
 // the sparse tile's LDS second-moment variant: fused mode, and the block fits the LDS the

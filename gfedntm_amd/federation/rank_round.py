@@ -34,7 +34,8 @@ from typing import Dict, List, Optional
 
 import torch
 
-from ..parallel.aggregator import (LOCAL_ALL, LOCAL_BCAST, LOCAL_FIRST, CollectiveAggregator,
+from ..parallel.aggregator import (LOCAL_ALL, LOCAL_BCAST, LOCAL_FIRST, LOCAL_REFRESH,
+                                   LOCAL_SHARED, LOCAL_SHARED_ALL, CollectiveAggregator,
                                    local_fedavg, prepare_local_fedavg)
 from ..utils.misc import graph_capture
 from .client import FederatedClient
@@ -94,10 +95,11 @@ class SingleClientRound:
                 e._capture(k)
             k *= 2
 
-    def step(self, it: int, hb=None, k: int = 1):
+    def step(self, it: int, hb=None, k: int = 1, more: bool = False):
         """Enqueue round ``it`` (k > 1: rounds it .. it + k - 1 in one replay); ``hb``
         (parallel/heartbeat.py) is marked in the all-reduce phase once the local step is
-        enqueued (a peer stuck before its step is then behind this rank)."""
+        enqueued (a peer stuck before its step is then behind this rank).  ``more``
+        (MultiClientRound.step) changes nothing for one client."""
         c = self.client
         if k > 1:
             if k > self.rounds_per_replay():
@@ -207,7 +209,16 @@ class MultiClientRound:
         self.fold_plan: Optional[str] = None   # the in-rank FedAvg of the batched round
         self._g = None                    # the one-round graph
         self._gk: Dict[int, object] = {}  # k-round graphs (k > 1)
-        self._bss: Dict[int, object] = {}  # the BatchedSteps each graph was captured with
+        self._gm: Dict[int, object] = {}  # k-round graphs whose last fold writes S only (more)
+        self._bss: Dict[tuple, object] = {}  # the BatchedSteps each graph was captured with
+        # the shared-reads plan (one rank, no collective): the batched kernels read the shared
+        # prefix from ONE copy S and the fold writes the sum there -- None: not decided yet,
+        # else whether it runs.  _s_live: S holds the averaged state and the clients' buffers
+        # do not (the last replay was a step(more=True))
+        self._shared_plan: Optional[bool] = None
+        self._shared_why: Optional[str] = None   # why not, once decided
+        self._S: Optional[torch.Tensor] = None
+        self._s_live = False
         self._gens = None
         self._streams = None
         self._side = None
@@ -267,9 +278,7 @@ class MultiClientRound:
             return
         engines = [c.tm.engine for c in self.clients]
         if self._gens != tuple(e.graph_gen for e in engines):
-            self._g = None
-            self._gk.clear()
-            self._bss.clear()
+            self._drop_graphs()
         if self._g is None:
             self._capture()
         k = 2
@@ -277,8 +286,39 @@ class MultiClientRound:
             if k not in self._gk:
                 self._capture(k)
             k *= 2
+        k = 1
+        while self._shared_plan and k <= kmax:
+            if k not in self._gm:
+                self._capture(k, more=True)
+            k *= 2
 
-    def _capture(self, k: int = 1):
+    def _drop_graphs(self):
+        self._g = None
+        self._gk.clear()
+        self._gm.clear()
+        self._bss.clear()
+
+    def _shared_reads(self, bs) -> Optional[str]:
+        """Decide the shared-reads plan at the first capture (GFEDNTM_SHARED_READS = auto |
+        0 | 1; auto and 1 take it where it applies) and return why it does not run (None: it
+        runs).  Every client must start from the same state, as for the in-epilogue fold."""
+        if self._shared_plan is None:
+            why = None
+            if os.environ.get("GFEDNTM_SHARED_READS", "auto") == "0":
+                why = "GFEDNTM_SHARED_READS=0"
+            elif self.colls:
+                why = "a collective follows the fold"
+            else:
+                why = bs.shared_reads_reason()
+                if why is None and not self._states_equal():
+                    why = "client states differ"
+            self._shared_plan = why is None
+            self._shared_why = why
+            if why is None:
+                self._S = torch.empty_like(self.shared[0])
+        return None if self._shared_plan else self._shared_why
+
+    def _capture(self, k: int = 1, more: bool = False):
         engines = [c.tm.engine for c in self.clients]
         for e in engines:
             e.prepare_external_capture()
@@ -307,6 +347,20 @@ class MultiClientRound:
                     self.fold_plan = fold
                 else:
                     self.fold_plan = "fold kernel (%s)" % (why or "client states differ")
+            # one rank: the kernels read ONE copy S of the shared prefix and write the
+            # clients' own buffers, and the fold writes the client-order sum to S alone --
+            # and to every client's buffer after the last round of a replay the host may
+            # look behind (not ``more``).  Same bits as the fold kernel's plan.
+            shared = False
+            if fold is None and os.environ.get("GFEDNTM_FOLD", "0") != "1":
+                why = self._shared_reads(bs)
+                if why is None:
+                    bs.set_shared_reads(self._S)
+                    bs.prepare()
+                    shared = True
+                    self.fold_plan = "shared reads + fold kernel"
+                elif why != "GFEDNTM_SHARED_READS=0" and not self.colls:
+                    self.fold_plan = "fold kernel (%s)" % why
             # beta's / adapt_bert's shares on the side stream once the backward has
             # finished them (else reduced with the rest at the end of the round: the same
             # arithmetic)
@@ -317,10 +371,16 @@ class MultiClientRound:
                         hooks[at] = (lambda p=part: self._fork(p))
                         forked.add(part)
             with graph_capture(g):
-                for _ in range(k):
+                for r in range(k):
                     bs.launch(after=hooks or None)
                     if fold is not None:
                         continue              # the FedAvg ran in the update epilogues
+                    if shared:
+                        a, b = self.parts["rest"]
+                        last = r == k - 1 and not more
+                        local_fedavg(self.shared, LOCAL_SHARED_ALL if last else LOCAL_SHARED,
+                                     off=a, n=b - a, dst=self._S)
+                        continue
                     if self.coll_in_graph or not self.colls:
                         for part in self.parts:
                             if part not in forked:
@@ -330,7 +390,7 @@ class MultiClientRound:
                     else:
                         self._fold("rest", LOCAL_FIRST)
             self._batched = bs
-            self._bss[k] = bs             # (its device tables are baked into the graph)
+            self._bss[(k, more)] = bs     # (its device tables are baked into the graph)
         else:
             self.fold_plan = "per-client graph branches + fold kernel"
             if self._streams is None:
@@ -353,15 +413,35 @@ class MultiClientRound:
                             self._reduce_part(part)
                     else:
                         self._fold("rest", LOCAL_FIRST)
-        if k == 1:
+        if more:
+            self._gm[k] = g
+        elif k == 1:
             self._g = g
         else:
             self._gk[k] = g
         self._gens = tuple(e.graph_gen for e in engines)
 
-    def step(self, it: int, hb=None, k: int = 1):
+    def _replay(self, k: int, more: bool):
+        """Replay the k-round graph.  Shared reads: S is refreshed from client 0's buffer
+        first unless the previous replay left the state in S alone (it was a ``more`` one),
+        so anything the host wrote into the clients' buffers since is what the rounds read;
+        after a ``more`` replay the state lives in S until the next replay."""
+        more = bool(more and self._shared_plan)
+        g = self._gm.get(k) if more else (self._g if k == 1 else self._gk.get(k))
+        if g is None:
+            self._capture(k, more)
+            g = self._gm[k] if more else (self._g if k == 1 else self._gk[k])
+        if self._shared_plan and not self._s_live:
+            local_fedavg(self.shared, LOCAL_REFRESH, dst=self._S)
+        g.replay()
+        self._s_live = more
+
+    def step(self, it: int, hb=None, k: int = 1, more: bool = False):
         """Rounds it .. it + k - 1 (k > 1: one replay of the k-round graph; the caller
-        keeps every round that needs the host between rounds out of such a run)."""
+        keeps every round that needs the host between rounds out of such a run).  ``more``:
+        the caller promises that the next thing to touch the clients' shared state is the
+        next step() -- no host read or write of it in between -- so the shared-reads plan
+        may leave the averaged state in its shared copy alone.  False is always safe."""
         if k > 1:
             if not self.graph or k > self.rounds_per_replay():
                 raise ValueError(f"{k} rounds per replay on this round object")
@@ -369,32 +449,24 @@ class MultiClientRound:
             for e in engines:
                 e.sync_step_counter(it)
             if self._gens != tuple(e.graph_gen for e in engines):
-                self._g = None
-                self._gk.clear()
-                self._bss.clear()
-            if k not in self._gk:
-                self._capture(k)
-            self._gk[k].replay()
+                self._drop_graphs()
+            self._replay(k, more)
             for e in engines:
                 e.advance_host_step(it + k - 1)
             if hb is not None:
                 for r in range(it, it + k):
                     hb.mark(r, 1)
             return
-        self._step1(it, hb)
+        self._step1(it, hb, more)
 
-    def _step1(self, it: int, hb=None):
+    def _step1(self, it: int, hb=None, more: bool = False):
         if self.graph:
             engines = [c.tm.engine for c in self.clients]
             for e in engines:
                 e.sync_step_counter(it)
             if self._gens != tuple(e.graph_gen for e in engines):
-                self._g = None
-                self._gk.clear()
-                self._bss.clear()
-            if self._g is None:
-                self._capture()
-            self._g.replay()
+                self._drop_graphs()
+            self._replay(1, more)
             for e in engines:
                 e.advance_host_step(it)
             if hb is not None:
@@ -495,9 +567,7 @@ class MultiClientRound:
         return {k: c.xgmi.debug_state() for k, c in self.colls.items() if c.xgmi is not None}
 
     def close(self):
-        self._g = None
-        self._gk.clear()
-        self._bss.clear()
+        self._drop_graphs()
         for c in self.colls.values():
             if c.xgmi is not None:
                 c.xgmi.close()

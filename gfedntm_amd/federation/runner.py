@@ -805,14 +805,17 @@ def _round_loop(rr, clients, client_ids, cmap, world, rank, device, ctrl, hb, lo
         if timing_warmup:
             ends.add(start + timing_warmup - 1)
 
+    def host_after(r: int) -> bool:
+        """The host needs the state, or the device, after round r."""
+        n1 = r + 1
+        return bool(r in ends
+                    or (poll_every and n1 % poll_every == 0) or (digest_every and n1 % digest_every == 0)
+                    or (metrics_every and n1 % metrics_every == 0)
+                    or (checkpoint_dir and checkpoint_every and n1 % checkpoint_every == 0))
+
     def run_end(it: int) -> int:
         r = it
-        while r < it + kmax - 1 and r not in ends:
-            n1 = r + 1
-            if ((poll_every and n1 % poll_every == 0) or (digest_every and n1 % digest_every == 0)
-                    or (metrics_every and n1 % metrics_every == 0)
-                    or (checkpoint_dir and checkpoint_every and n1 % checkpoint_every == 0)):
-                break
+        while r < it + kmax - 1 and not host_after(r):
             r += 1
         return r
 
@@ -827,10 +830,12 @@ def _round_loop(rr, clients, client_ids, cmap, world, rank, device, ctrl, hb, lo
                 # (a power of two: at most log2(kmax) + 1 graphs are ever captured -- a
                 # capture inside the timed rounds costs milliseconds)
                 k = 1 << ((run_end(it) - it + 1).bit_length() - 1) if kmax > 1 else 1
+                # (more: the next replay follows with no host access to the state in between)
+                more = kmax > 1 and not host_after(it + k - 1)
                 if k > 1:
-                    rr.step(it, hb, k)
+                    rr.step(it, hb, k, more=more)
                 else:
-                    rr.step(it, hb)
+                    rr.step(it, hb, more=more)
                 covered = it + k - 1
             elif hb is not None:
                 hb.mark(it, 1)

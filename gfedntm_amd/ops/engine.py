@@ -1691,6 +1691,7 @@ class BatchedSteps:
         self._cu = torch.cuda.get_device_properties(self.device).multi_processor_count
         self._fold = None                 # abi.GfkFold when the FedAvg runs in the epilogues
         self._fold_left = None            # its device table of leftover pieces
+        self._shared = None               # the shared read copy S (set_shared_reads)
 
     @staticmethod
     def possible(engines) -> bool:
@@ -1806,8 +1807,12 @@ class BatchedSteps:
             # they exceed two rounds of 16-wave workgroups
             if M * (mm.n_tiles + 8) > 2 * self._cu:
                 mm.stage_flags |= STAGE_WIN_BATCH8
+            uu = e._u
+            if self._shared is not None:
+                uu = abi.GfkUpdate.from_buffer_copy(bytes(e._u))
+                self._point_at_shared(e, mm, uu)
             ms.append(bytes(mm))
-            us.append(bytes(e._u))
+            us.append(bytes(uu))
         # the phases of the batched plan: post_fwd out where the launch folds it, back in
         # where the launch dropped the engines' fold
         ph = list(self.engines[0].phases())
@@ -1831,6 +1836,98 @@ class BatchedSteps:
     def prepare(self):
         """Upload the descriptors now (before a capture)."""
         self._refresh()
+
+    # ---- one shared read copy of the shared prefix (csrc/gfk_common.h GfkModel.off_own) ----
+    def _shared_range(self, e):
+        lo = e.flat.buffer.data_ptr()
+        return lo, lo + 4 * e.flat.n_shared
+
+    def shared_reads_reason(self) -> Optional[str]:
+        """Why this launch cannot read one shared copy of the shared prefix (None: it can).
+        The kernels converted to GfkModel.off_own are those of a ProdLDA bag-of-words step
+        with fused Adam epilogues: the strip / tile forward, post_fwd, the decoder backward
+        without a precomputed logit gradient, win_update's dense and sparse tiles and jobs.
+        Every tensor they update must lie in the shared prefix (its pointer then addresses
+        S, and its new value, moments and gradient slot the client's buffer)."""
+        e0 = self.engines[0]
+        m = self._host if self._host is not None else e0._m
+        checks = [
+            (len(self.engines) > 1, "one client"),
+            (m.kind == abi.KIND_PRODLDA, "ProdLDA only"),
+            (m.input == abi.IN_BOW and not m.lab_on, "bag-of-words input without a label head"),
+            (e0.update_mode == UPDATE_FUSED, "fused Adam epilogues only"),
+            (not m.bwd_pre, "the decoder backward without a precomputed logit gradient only"),
+            (not m.stage_flags & STAGE_LB, "not the large-batch plan"),
+        ]
+        for ok, why in checks:
+            if not ok:
+                return why
+        for e in self.engines:
+            fl, mm, uu = e.flat, e._m, e._u
+            if not mm.fed_scale_on:
+                return "no FedAvg pre-scale"
+            if fl.buffer.data_ptr() % 16:
+                return "a flat buffer off 16-byte alignment"
+            if any(s.offset + s.numel > fl.n_shared for s in fl.param_slots()):
+                return "a parameter outside the shared prefix"
+            lo, hi = self._shared_range(e)
+            written = [mm.beta, mm.w_in, mm.mu_rm, mm.mu_rv, mm.s_rm, mm.s_rv, mm.beta_rm, mm.beta_rv]
+            written += [uu.w[i].param for i in range(uu.n_w)] + [uu.v[i].param for i in range(uu.n_v)]
+            if not all(p is not None and lo <= int(p) < hi for p in written):
+                return "an updated tensor outside the shared prefix"
+        return None
+
+    def set_shared_reads(self, shared: Optional[torch.Tensor]):
+        """``shared``: n_shared floats every client READS its shared parameters and BN
+        buffers from (the descriptors' pointers into the shared prefix address it); the
+        kernels store the new values, and keep the Adam moments and gradient slots, in the
+        client's own flat buffer.  The caller keeps ``shared`` equal to what every client
+        would hold at the start of each step (rank_round.MultiClientRound).  None: off."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("set_shared_reads inside a graph capture")
+        if shared is not None:
+            why = self.shared_reads_reason()
+            if why is not None:
+                raise ValueError(f"shared reads not available: {why}")
+            if self._fold is not None:
+                raise ValueError("shared reads and the in-epilogue FedAvg exclude each other")
+            n = self.engines[0].flat.n_shared
+            if (shared.dtype != torch.float32 or shared.device != self.device or shared.numel() != n
+                    or not shared.is_contiguous() or shared.data_ptr() % 16
+                    or any(e.flat.n_shared != n for e in self.engines)):
+                raise ValueError("the shared read copy: n_shared contiguous float32 on the "
+                                 "engines' device, 16-byte aligned")
+        self._shared = shared
+
+    def _point_at_shared(self, e, mm, uu):
+        """Rebase every pointer of the client's descriptors that lies in its shared prefix
+        onto the shared copy; off_own leads back to the client's buffer, and the moment /
+        gradient offsets are taken from the rebased pointers."""
+        lo, hi = self._shared_range(e)
+        delta = self._shared.data_ptr() - lo
+        if delta % 16:
+            raise ValueError("the shared read copy is not 16 bytes from the client's buffer")
+
+        def move(st, name):
+            v = getattr(st, name)
+            if isinstance(v, C.Array):
+                for i in range(len(v)):
+                    if v[i] is not None and lo <= v[i] < hi:
+                        v[i] = v[i] + delta
+            elif v is not None and lo <= v < hi:
+                setattr(st, name, v + delta)
+
+        for name, typ in abi.GfkModel._fields_:
+            if typ is abi.P or (isinstance(typ, type) and issubclass(typ, C.Array)
+                                and typ._type_ is abi.P):
+                move(mm, name)
+        for i in range(uu.n_w):
+            move(uu.w[i], "param")
+        for i in range(uu.n_v):
+            move(uu.v[i], "param")
+        own = -delta // 4
+        mm.off_own = own
+        mm.off_m, mm.off_v, mm.off_g = mm.off_m + own, mm.off_v + own, mm.off_g + own
 
     # ---- the FedAvg in the update epilogues (csrc/prodlda.hip gfk_bwd_fold_k,
     #      csrc/update.hip gfk_win_fold_k) ----
@@ -1907,6 +2004,8 @@ class BatchedSteps:
         why = self.fold_reason()
         if why is not None:
             raise ValueError(f"in-epilogue FedAvg not available: {why}")
+        if self._shared is not None:
+            raise ValueError("shared reads and the in-epilogue FedAvg exclude each other")
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("set_fold inside a graph capture")
         e0 = self.engines[0]

@@ -128,6 +128,7 @@ class GfkModel(C.Structure):
         ("dev", P), ("dev_upd", P), ("n_batch", C.c_int32), ("ldb", C.c_int32),
         ("ctx_bgrid", C.c_int32), ("ws_colstat", P),
         ("kl_hist", P), ("rl_hist", P),
+        ("off_own", C.c_int64),
     ]
 
 

@@ -253,10 +253,22 @@ class CollectiveAggregator:
 class _GfkLocalAvg(ctypes.Structure):
     _fields_ = [("f", ctypes.c_void_p), ("gend", ctypes.c_void_p), ("off", ctypes.c_int64),
                 ("n", ctypes.c_int64), ("n_clients", ctypes.c_int32), ("mode", ctypes.c_int32),
-                ("n_groups", ctypes.c_int32), ("pad", ctypes.c_int32)]
+                ("n_groups", ctypes.c_int32), ("pad", ctypes.c_int32), ("dst", ctypes.c_void_p)]
+
+
+LOCAL_V_MAX = 8       # clients whose pointers fit gfk_local_fedavg_v's arguments (csrc/comm.hip FV)
+
+
+class _GfkLocalAvgV(ctypes.Structure):
+    _fields_ = [("f", ctypes.c_void_p * LOCAL_V_MAX), ("dst", ctypes.c_void_p),
+                ("off", ctypes.c_int64), ("n", ctypes.c_int64), ("n_clients", ctypes.c_int32),
+                ("mode", ctypes.c_int32)]
 
 
 LOCAL_ALL, LOCAL_FIRST, LOCAL_BCAST = 0, 1, 2     # gfk_local_fedavg modes (csrc/comm.hip)
+# with a shared read copy ``dst``: the sum into dst only / into dst and every buffer / the
+# refresh dst <- flats[0]
+LOCAL_SHARED, LOCAL_SHARED_ALL, LOCAL_REFRESH = 3, 4, 5
 
 # device tables of the in-process fold (client buffer pointers + group ends), one per
 # (device, pointers, groups): built outside graph captures, kept alive for the graphs
@@ -291,20 +303,27 @@ def prepare_local_fedavg(flats: Sequence[torch.Tensor], groups: Optional[Sequenc
 
 
 def local_fedavg(flats: Sequence[torch.Tensor], mode: int = LOCAL_ALL,
-                 groups: Optional[Sequence[int]] = None, off: int = 0, n: Optional[int] = None):
+                 groups: Optional[Sequence[int]] = None, off: int = 0, n: Optional[int] = None,
+                 dst: Optional[torch.Tensor] = None):
     """One launch of csrc/comm.hip ``gfk_local_fedavg`` on the current stream (capture
     safe once :func:`prepare_local_fedavg` ran on the same buffers): the group-wise left-
     fold sum of ``flats`` (``groups``: sizes of consecutive client groups, default one
     group) written to every buffer (LOCAL_ALL) or to flats[0] only (LOCAL_FIRST), or
     flats[0] copied to the others (LOCAL_BCAST).  ``off`` / ``n``: the float range folded
-    (default the whole buffers).  Any number of clients."""
+    (default the whole buffers).  Any number of clients.  ``dst`` (LOCAL_SHARED /
+    LOCAL_SHARED_ALL / LOCAL_REFRESH): the shared read copy the sum, or flats[0], is written
+    to, over the same range; up to LOCAL_V_MAX clients in one group take the kernel with the
+    pointers in its arguments (no device table)."""
     C = ctypes
     from ..ops import native
     lib = native.kernels()
     if not getattr(lib, "_gfk_local_avg_declared", False):
         lib.gfk_local_avg_struct_size.restype = C.c_size_t
+        lib.gfk_local_avg_v_struct_size.restype = C.c_size_t
         lib.gfk_local_fedavg_launch.argtypes = [C.POINTER(_GfkLocalAvg), C.c_int, C.c_void_p]
-        if lib.gfk_local_avg_struct_size() != C.sizeof(_GfkLocalAvg):
+        lib.gfk_local_fedavg_v_launch.argtypes = [C.POINTER(_GfkLocalAvgV), C.c_void_p]
+        if (lib.gfk_local_avg_struct_size() != C.sizeof(_GfkLocalAvg)
+                or lib.gfk_local_avg_v_struct_size() != C.sizeof(_GfkLocalAvgV)):
             raise RuntimeError("GfkLocalAvg ABI mismatch between csrc/comm.hip and aggregator.py")
         lib._gfk_local_avg_declared = True
     groups = [len(flats)] if groups is None else [int(g) for g in groups]
@@ -314,15 +333,35 @@ def local_fedavg(flats: Sequence[torch.Tensor], mode: int = LOCAL_ALL,
     n = total - off if n is None else int(n)
     if off % 4 or off < 0 or off + n > total or any(f.numel() != total for f in flats):
         raise ValueError(f"bad local_fedavg range [{off}, {off + n}) of {total}")
+    stream = torch.cuda.current_stream(flats[0].device).cuda_stream
+    if mode >= LOCAL_SHARED:
+        if (dst is None or dst.device != flats[0].device or dst.dtype != torch.float32
+                or not dst.is_contiguous() or dst.numel() < off + n or dst.data_ptr() % 16):
+            raise ValueError("local_fedavg: this mode needs a 16-byte aligned float32 dst "
+                             "covering the range on the buffers' device")
+        if len(flats) <= LOCAL_V_MAX and len(groups) == 1:
+            if any(f.data_ptr() % 16 for f in flats):
+                raise ValueError("local_fedavg buffers must be 16-byte aligned")
+            v = _GfkLocalAvgV()
+            for j, f in enumerate(flats):
+                v.f[j] = f.data_ptr()
+            v.dst, v.off, v.n = dst.data_ptr(), int(off), n
+            v.n_clients, v.mode = len(flats), int(mode)
+            rc = lib.gfk_local_fedavg_v_launch(C.byref(v), C.c_void_p(stream))
+            if rc:
+                raise RuntimeError(f"gfk_local_fedavg_v_launch failed ({rc})")
+            return v
+    elif dst is not None:
+        raise ValueError("local_fedavg: dst goes with the LOCAL_SHARED* / LOCAL_REFRESH modes")
     table = _local_table(flats, groups)
     d = _GfkLocalAvg()
     d.f = table.data_ptr()
     d.gend = table.data_ptr() + 8 * len(flats)
     d.off, d.n = int(off), n
     d.n_clients, d.mode, d.n_groups = len(flats), int(mode), len(groups)
+    d.dst = dst.data_ptr() if dst is not None else None
     cu = torch.cuda.get_device_properties(flats[0].device).multi_processor_count
     grid = int(max(1, min(-(-n // 1024), 4 * cu)))
-    stream = torch.cuda.current_stream(flats[0].device).cuda_stream
     rc = lib.gfk_local_fedavg_launch(C.byref(d), grid, C.c_void_p(stream))
     if rc:
         raise RuntimeError(f"gfk_local_fedavg_launch failed ({rc})")
