@@ -228,8 +228,8 @@ class MultiClientRound:
                         len(clients), self.method or "no collective", world)
 
     def _states_equal(self) -> bool:
-        """Every client's shared state is the same (the in-epilogue fold reads client 0's
-        copy for all of them): true after W0's broadcast and after every FedAvg."""
+        """Every client's shared state is the same (the shared-reads plan has all of them
+        read one copy): true after W0's broadcast and after every FedAvg."""
         s0 = self.shared[0]
         return all(torch.equal(s0, s) for s in self.shared[1:])
 
@@ -301,7 +301,7 @@ class MultiClientRound:
     def _shared_reads(self, bs) -> Optional[str]:
         """Decide the shared-reads plan at the first capture (GFEDNTM_SHARED_READS = auto |
         0 | 1; auto and 1 take it where it applies) and return why it does not run (None: it
-        runs).  Every client must start from the same state, as for the in-epilogue fold."""
+        runs).  Every client must start from the same state (_states_equal)."""
         if self._shared_plan is None:
             why = None
             if os.environ.get("GFEDNTM_SHARED_READS", "auto") == "0":
@@ -332,35 +332,19 @@ class MultiClientRound:
         if batched:
             bs = BatchedSteps(engines)
             bs.prepare()
-            # one rank, GFEDNTM_FOLD=1: the round's FedAvg inside the update kernels' epilogues
-            # (every client starts each round from the same averaged state) -- bit-identical
-            # to the default, the batched steps + the fold kernel, but measured slower at the
-            # headline (0.1355 vs 0.1174 ms per round, profiles/r6/README.md): opt-in
-            fold = None
             self.fold_plan = "fold kernel" + (" + all-reduce" if self.colls else "")
-            if not self.colls and os.environ.get("GFEDNTM_FOLD", "0") == "1":
-                why = bs.fold_reason()
-                if why is None and self._states_equal():
-                    from ..ops import kernel_abi as abi
-                    bs.set_fold(abi.FOLD_ALL)
-                    fold = "in-epilogue"
-                    self.fold_plan = fold
-                else:
-                    self.fold_plan = "fold kernel (%s)" % (why or "client states differ")
             # one rank: the kernels read ONE copy S of the shared prefix and write the
             # clients' own buffers, and the fold writes the client-order sum to S alone --
             # and to every client's buffer after the last round of a replay the host may
             # look behind (not ``more``).  Same bits as the fold kernel's plan.
-            shared = False
-            if fold is None and os.environ.get("GFEDNTM_FOLD", "0") != "1":
-                why = self._shared_reads(bs)
-                if why is None:
-                    bs.set_shared_reads(self._S)
-                    bs.prepare()
-                    shared = True
-                    self.fold_plan = "shared reads + fold kernel"
-                elif why != "GFEDNTM_SHARED_READS=0" and not self.colls:
-                    self.fold_plan = "fold kernel (%s)" % why
+            why = self._shared_reads(bs)
+            shared = why is None
+            if shared:
+                bs.set_shared_reads(self._S)
+                bs.prepare()
+                self.fold_plan = "shared reads + fold kernel"
+            elif why != "GFEDNTM_SHARED_READS=0" and not self.colls:
+                self.fold_plan = "fold kernel (%s)" % why
             # beta's / adapt_bert's shares on the side stream once the backward has
             # finished them (else reduced with the rest at the end of the round: the same
             # arithmetic)
@@ -373,8 +357,6 @@ class MultiClientRound:
             with graph_capture(g):
                 for r in range(k):
                     bs.launch(after=hooks or None)
-                    if fold is not None:
-                        continue              # the FedAvg ran in the update epilogues
                     if shared:
                         a, b = self.parts["rest"]
                         last = r == k - 1 and not more

@@ -213,7 +213,7 @@ class LocalFederation:
         self.round_batched = (round_batched if round_batched is not None else
                               os.environ.get("GFEDNTM_ROUND_BATCHED", "1") == "1")
         self._batched = None
-        self.fold_plan: Optional[str] = None    # the batched round's FedAvg (in-epilogue / kernel)
+        self.fold_plan: Optional[str] = None    # the batched round's FedAvg plan
         self._rg = None
         self._rgk = {}                    # k -> (the k-round graph, the launches it baked in)
         self._rg_gens = None
@@ -260,20 +260,12 @@ class LocalFederation:
                 self._batched = self._batched_parts[0]
                 for b in self._batched_parts:
                     b.prepare()
-                # one group, GFEDNTM_FOLD=1: the FedAvg inside the update kernels' epilogues
-                # (rank_round.MultiClientRound: opt-in, measured slower than the fold kernel)
-                fold = (len(self._batched_parts) == 1 and os.environ.get("GFEDNTM_FOLD", "0") == "1"
-                        and self._batched.fold_reason() is None
-                        and all(torch.equal(shared[0], x) for x in shared[1:]))
-                if fold:
-                    from ..ops import kernel_abi as abi
-                    self._batched.set_fold(abi.FOLD_ALL)
-                self.fold_plan = "in-epilogue" if fold else "fold kernel"
+                self.fold_plan = "fold kernel"
                 with graph_capture(g):
                     for _ in range(k):
                         for b in self._batched_parts:
                             b.launch()
-                        if not fold and not self.agg.fused_sum_(shared):
+                        if not self.agg.fused_sum_(shared):
                             raise RuntimeError("round graph needs the native FedAvg kernel")
                 self._store_round_graph(g, k)
                 return

@@ -233,17 +233,7 @@ def _force_k_split(lib, m) -> bool:
 def lds_required(tm, bmax: int) -> int:
     """Largest dynamic LDS any fused kernel needs for this model (weights unstaged),
     as computed by the kernel library itself."""
-    m = abi.GfkModel()
-    hs = list(tm.hidden_sizes)
-    m.bmax, m.V, m.K, m.n_hidden = bmax, tm.input_size, tm.n_components, len(hs)
-    m.ldb = beta_ld(m.V)
-    for i, h in enumerate(hs):
-        m.H[i] = h
-    m.kind = abi.KIND_PRODLDA if tm.model_type.lower() == "prodlda" else abi.KIND_LDA
-    m.mm_bf16 = int(getattr(tm, "matmul_dtype", "fp32") == "bf16")
-    m.kt = theta_stride(m.K)
-    m.vb, m.n_tiles = VB, -(-m.V // VB)
-    m.n_dpart = m.n_tiles if m.kind == abi.KIND_PRODLDA else 1
+    m = _shape_model(tm, bmax)
     lib = native.kernels()
     which = (0, 1) if m.kind == abi.KIND_PRODLDA else (2, 3)
     if uses_large_batch_plan(tm, bmax):
@@ -600,8 +590,8 @@ class FusedEngine(EngineBase):
                 # statistics lengthen the forward's critical path more than the launch they
                 # save (interleaved, one box: 0.0601 vs 0.0597 ms per round,
                 # profiles/r5/ab_fold.txt).  GFEDNTM_POSTFOLD=1 forces it here, =0 everywhere
-                self._fold_ok = bool(m.K <= 64 and not m.lab_on)
-                if self._fold_ok and os.environ.get("GFEDNTM_POSTFOLD", "auto") == "1":
+                self._postfold_ok = bool(m.K <= 64 and not m.lab_on)
+                if self._postfold_ok and os.environ.get("GFEDNTM_POSTFOLD", "auto") == "1":
                     m.stage_flags |= STAGE_FWD_POSTFOLD
             # backward: one workgroup per tile while the tiles fit the resident slots;
             # else persistent, n_dpart d theta_d slabs: with >= 4 k tiles the topics
@@ -1689,8 +1679,6 @@ class BatchedSteps:
         self._host = None
         self._phases = e0.phases()
         self._cu = torch.cuda.get_device_properties(self.device).multi_processor_count
-        self._fold = None                 # abi.GfkFold when the FedAvg runs in the epilogues
-        self._fold_left = None            # its device table of leftover pieces
         self._shared = None               # the shared read copy S (set_shared_reads)
 
     @staticmethod
@@ -1737,24 +1725,20 @@ class BatchedSteps:
             # wave), T the FEWEST in 1..4 whose M ceil(n_tiles / T) workgroups still fit one
             # round -- T = 3 at M = 8, V = 4.7k: 192 workgroups of 12 busy waves instead of
             # 144 of 16; past 4 tiles the M clients share one round (dec_grid = CUs / M).
-            # GFEDNTM_BATCH_STRIP=keep: the engines' own grids (rounds of the CUs).
-            if (mm.stage_flags & STAGE_FWD_STRIP and M > 1 and M * mm.dec_grid > self._cu
-                    and os.environ.get("GFEDNTM_BATCH_STRIP", "fill") != "keep"):
-                t = next((t for t in (1, 2, 3, 4) if M * -(-mm.n_tiles // t) <= self._cu), None)
-                mm.dec_grid = -(-mm.n_tiles // t) if t else max(1, self._cu // M)
             # NeuralLDA's decoder kernels (beta forward / backward, grid-strided over the
             # tiles) likewise: T tiles per workgroup so the M clients' workgroups fit one
             # round of the CUs -- the backward's theta_d staging is then paid once per T
             # tiles (8 clients, V = 4.7k: 0.1426 -> 0.1407 ms, same bits; one round of two
             # workgroups per CU measured 0.1497, profiles/r6/lda/ab_batch_fill.txt).
-            # GFEDNTM_BATCH_STRIP=keep: the engines' own grids here too.
-            if (mm.kind == abi.KIND_LDA and M > 1 and M * mm.dec_grid > self._cu
+            # GFEDNTM_BATCH_STRIP=keep: the engines' own grids (rounds of the CUs).
+            if ((mm.stage_flags & STAGE_FWD_STRIP or mm.kind == abi.KIND_LDA)
+                    and M > 1 and M * mm.dec_grid > self._cu
                     and os.environ.get("GFEDNTM_BATCH_STRIP", "fill") != "keep"):
                 t = next((t for t in (1, 2, 3, 4) if M * -(-mm.n_tiles // t) <= self._cu), None)
                 mm.dec_grid = -(-mm.n_tiles // t) if t else max(1, self._cu // M)
             # the posterior folded into the strip forward for M > 1 clients (the engines' own
             # plan keeps post_fwd for one client; GFEDNTM_POSTFOLD=0: never)
-            if (M > 1 and getattr(e, "_fold_ok", False) and mm.stage_flags & STAGE_FWD_STRIP
+            if (M > 1 and getattr(e, "_postfold_ok", False) and mm.stage_flags & STAGE_FWD_STRIP
                     and os.environ.get("GFEDNTM_POSTFOLD", "auto") != "0"):
                 mm.stage_flags |= STAGE_FWD_POSTFOLD
             # post_bwd: M clients x (bmax + 1) workgroups of 16 waves with the batch matrices
@@ -1830,8 +1814,6 @@ class BatchedSteps:
             self._arr_u.copy_(torch.frombuffer(bytearray(b"".join(us)), dtype=torch.uint8))
             self._blob = blob
         self._host = abi.GfkModel.from_buffer_copy(ms[0])
-        if self._fold is not None:
-            self._upload_fold_table()
 
     def prepare(self):
         """Upload the descriptors now (before a capture)."""
@@ -1889,8 +1871,6 @@ class BatchedSteps:
             why = self.shared_reads_reason()
             if why is not None:
                 raise ValueError(f"shared reads not available: {why}")
-            if self._fold is not None:
-                raise ValueError("shared reads and the in-epilogue FedAvg exclude each other")
             n = self.engines[0].flat.n_shared
             if (shared.dtype != torch.float32 or shared.device != self.device or shared.numel() != n
                     or not shared.is_contiguous() or shared.data_ptr() % 16
@@ -1929,169 +1909,6 @@ class BatchedSteps:
         mm.off_own = own
         mm.off_m, mm.off_v, mm.off_g = mm.off_m + own, mm.off_v + own, mm.off_g + own
 
-    # ---- the FedAvg in the update epilogues (csrc/prodlda.hip gfk_bwd_fold_k,
-    #      csrc/update.hip gfk_win_fold_k) ----
-    FOLD_PIECE = 1024                     # floats per leftover workgroup (256 threads x float4)
-
-    def _fold_owned(self) -> Dict[int, str]:
-        """Flat offsets of the shared slots the fold kernels' update jobs own (beta, W_in,
-        every weight / vector job's parameter) -> key."""
-        e0 = self.engines[0]
-        base = e0.flat.buffer.data_ptr()
-        by_off = {s.offset: k for k, s in e0.flat.slots.items()}
-        owned = {}
-        ptrs = [int(e0._m.beta), int(e0._m.w_in)]
-        ptrs += [int(e0._u.w[i].param) for i in range(e0._u.n_w)]
-        ptrs += [int(e0._u.v[i].param) for i in range(e0._u.n_v)]
-        for p in ptrs:
-            off = (p - base) // 4
-            if (p - base) % 4 or off not in by_off:
-                raise ValueError("an update job's parameter is not a slot of the flat buffer")
-            owned[off] = by_off[off]
-        return owned
-
-    def fold_reason(self) -> Optional[str]:
-        """Why the in-epilogue FedAvg cannot run this launch (None: it can).  The fold
-        kernels cover the headline plan: ProdLDA, bag of words, fused Adam, fp32, bmax 64,
-        K and every hidden layer <= 64, one d theta_d slab per tile, dense W_in tiles,
-        every parameter in the shared prefix and pre-scaled."""
-        e0 = self.engines[0]
-        m = self._host if self._host is not None else e0._m
-        if not hasattr(e0.lib, "gfk_bwd_fold_launch"):
-            return "kernel library without the fold kernels"
-        checks = [
-            (m.kind == abi.KIND_PRODLDA, "ProdLDA only"),
-            (m.input == abi.IN_BOW and not m.lab_on, "bag-of-words input without a label head"),
-            (e0.update_mode == UPDATE_FUSED, "fused Adam epilogues only"),
-            (not m.mm_bf16, "fp32 GEMM operands only"),
-            (m.K <= 64 and m.bmax == 64, "K <= 64 and batch 64 only"),
-            (max(int(m.H[i]) for i in range(m.n_hidden)) <= 64, "hidden layers <= 64 only"),
-            (not m.bwd_pre and m.n_dpart == m.n_tiles,
-             "the one-slab-per-tile backward only"),
-            (not m.stage_flags & (STAGE_WIN_SPARSE | STAGE_LB),
-             "dense W_in tiles only"),
-            (m.kt % 2 == 0, "theta_d stride"),
-            (all(e0._u.v[i].n <= 64 for i in range(e0._u.n_v)), "vector jobs <= 64 long"),
-            (e0._u.n_w <= abi.FOLD_W and e0._u.n_v <= abi.FOLD_V, "too many update jobs"),
-        ]
-        for ok, why in checks:
-            if not ok:
-                return why
-        for e in self.engines:
-            fl = e.flat
-            if any(s.offset + s.numel > fl.n_shared for s in fl.param_slots()):
-                return "a parameter outside the shared prefix"
-            if not e._m.fed_scale_on:
-                return "no FedAvg pre-scale"
-        try:
-            owned = self._fold_owned()
-        except ValueError as exc:
-            return str(exc)
-        fl = e0.flat
-        for k in fl.shared_keys:
-            s = fl.slots[k]
-            if s.offset not in owned and s.is_param:
-                return f"parameter {k} has no fold job"
-        return None
-
-    def set_fold(self, mode: Optional[int]):
-        """mode abi.FOLD_ALL / FOLD_FIRST: replace prodlda_bwd and win_update by the fold
-        kernels (the round's in-rank FedAvg inside their epilogues; every client's state must
-        be the same at the start of each round -- the caller's invariant); None: off."""
-        if mode is None:
-            self._fold = None
-            return
-        why = self.fold_reason()
-        if why is not None:
-            raise ValueError(f"in-epilogue FedAvg not available: {why}")
-        if self._shared is not None:
-            raise ValueError("shared reads and the in-epilogue FedAvg exclude each other")
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("set_fold inside a graph capture")
-        e0 = self.engines[0]
-        owned = self._fold_owned()
-        pieces = []
-        for k in e0.flat.shared_keys:
-            s = e0.flat.slots[k]
-            if s.offset in owned:
-                continue
-            for a in range(0, s.numel, self.FOLD_PIECE):
-                pieces += [s.offset + a, min(self.FOLD_PIECE, s.numel - a)]
-        if any(p % 4 for p in pieces[0::2]):
-            raise ValueError("leftover pieces must start on 16-byte boundaries")
-        self._fold_left = torch.tensor(pieces or [0, 0], dtype=torch.int64, device=self.device)
-        M = len(self.engines)
-        self._fold_cl = torch.zeros(M * C.sizeof(abi.GfkFoldClient), dtype=torch.uint8,
-                                    device=self.device)
-        self._fold_cl_bytes = None
-        f = abi.GfkFold()
-        f.models, f.upds = self._arr_m.data_ptr(), self._arr_u.data_ptr()
-        f.left = self._fold_left.data_ptr()
-        f.M, f.mode, f.n_left = M, int(mode), len(pieces) // 2
-        f.nj = -(-int(e0._m.H[0]) // 16)
-        f.cl = self._fold_cl.data_ptr()
-        self._fold = f
-        self._upload_fold_table()
-
-    @staticmethod
-    def _fold_client(e) -> "abi.GfkFoldClient":
-        """One client's pointer table for the fold kernels (csrc GfkFoldClient)."""
-        m, u = e._m, e._u
-        c = abi.GfkFoldClient()
-        base = int(m.flat_base)
-
-        def moments(p):
-            p = int(p)
-            return p, p + 4 * int(m.off_m), p + 4 * int(m.off_v)
-
-        def scale(p):
-            return float(m.fed_scale) if (m.fed_scale_on and (int(p) - base) // 4 < int(m.n_shared)) else 1.0
-
-        c.tstart, c.indices, c.values, c.nb = m.ws_tstart, m.indices, m.values, m.ws_nb
-        c.coef, c.zn, c.thetad, c.lse, c.s, c.rstd = (m.adam_coef, m.ws_zn, m.ws_thetad, m.ws_lse,
-                                                       m.ws_s, m.ws_col_rstd)
-        c.beta, c.beta_m, c.beta_v = moments(m.beta)
-        c.dthetad, c.dz0 = m.ws_dthetad, m.ws_dz[0]
-        c.w_in, c.w_in_m, c.w_in_v = moments(m.w_in)
-        c.flat = base
-        c.beta_sc, c.win_sc = scale(m.beta), scale(m.w_in)
-        c.b1, c.b2, c.eps, c.wd = m.beta1, m.beta2, m.adam_eps, m.weight_decay
-        for j in range(u.n_w):
-            J = u.w[j]
-            c.wdz[j], c.wa[j] = J.dz, J.a
-            c.wp[j], c.wm[j], c.wv[j] = moments(J.param)
-            c.wsc[j] = scale(J.param)
-        for j in range(u.n_v):
-            J = u.v[j]
-            c.vsrc[j] = J.src
-            c.vp[j], c.vm[j], c.vv[j] = moments(J.param)
-            c.vg[j] = int(J.param) + 4 * int(m.off_g)
-            c.vsc[j] = scale(J.param)
-        return c
-
-    def _upload_fold_table(self):
-        blob = b"".join(bytes(self._fold_client(e)) for e in self.engines)
-        if blob != self._fold_cl_bytes:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("fold client table changed inside a graph capture")
-            self._fold_cl.copy_(torch.frombuffer(bytearray(blob), dtype=torch.uint8))
-            self._fold_cl_bytes = blob
-
-    @property
-    def fold_mode(self) -> Optional[int]:
-        return None if self._fold is None else int(self._fold.mode)
-
-    def _run_fold(self, phase: int):
-        e0 = self.engines[0]
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        if phase == abi.PH_FOLD_BWD:
-            rc = e0.lib.gfk_bwd_fold_launch(C.byref(self._host), C.byref(self._fold), stream)
-        else:
-            rc = e0.lib.gfk_win_fold_launch(C.byref(self._host), C.byref(e0._u),
-                                            C.byref(self._fold), stream)
-        if rc:
-            raise RuntimeError(f"fold kernel launch failed: code {rc} (phase {phase})")
-
     def _run(self, phases):
         e0 = self.engines[0]
         arr, n = abi.phase_array(phases)
@@ -2106,25 +1923,16 @@ class BatchedSteps:
         {phase: callable} called (on the host, while enqueuing) right after that phase's
         launch -- the multi-client rank round forks beta's FedAvg there."""
         self._refresh()
-        after = dict(after or {})
-        phases = list(self._phases)
-        if self._fold is not None:
-            swap = {abi.PH_PRODLDA_BWD: abi.PH_FOLD_BWD, abi.PH_ENC_BWD: abi.PH_FOLD_WIN}
-            phases = [swap.get(p, p) for p in phases]
-            after = {swap.get(p, p): f for p, f in after.items()}
+        after = after or {}
         run: List[int] = []
-        for p in phases + [None]:
-            if p is not None and p not in (abi.PH_FOLD_BWD, abi.PH_FOLD_WIN):
-                run.append(p)
-                if p not in after:
-                    continue
-            if run:
+        for p in self._phases:           # one gfk_run per stretch, cut where a hook sits
+            run.append(p)
+            if p in after:
                 self._run(run)
                 run = []
-            if p in (abi.PH_FOLD_BWD, abi.PH_FOLD_WIN):
-                self._run_fold(p)
-            if p in after:
                 after[p]()
+        if run:
+            self._run(run)
 
     def wa_final_phase(self) -> Optional[int]:
         """The phase after which every client's adapt_bert (CombinedTM) is final in the

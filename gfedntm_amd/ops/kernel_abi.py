@@ -66,11 +66,7 @@ PH_FEDAVG_WA = 107
 # d theta_d after prodlda_lb_dlogit (PH_PRODLDA_BWD)
 PH_LB_GEMM_FWD = 108
 PH_LB_GEMM_BWD = 109
-# batched clients with the FedAvg in the update epilogues (ops/engine.py BatchedSteps.set_fold):
-# csrc/prodlda.hip gfk_bwd_fold_k in place of PH_PRODLDA_BWD, csrc/update.hip gfk_win_fold_k
-# in place of PH_ENC_BWD (launched by the batched plan, not by gfk_run)
-PH_FOLD_BWD = 110
-PH_FOLD_WIN = 111
+# (110 - 111: round 6's in-epilogue FedAvg phases, removed in round 10)
 HOST_PHASES = (PH_CTX_FWD, PH_CTX_BWD, PH_FEDAVG_BETA, PH_FEDAVG_END, PH_FEDAVG_WA, PH_LB_GEMM_FWD,
                PH_LB_GEMM_BWD)
 
@@ -223,38 +219,10 @@ class GfkThin(C.Structure):
 
 THIN_COUNT, THIN_COMPACT = 1, 2
 
-FOLD_W, FOLD_V = 8, 16
-
-
-class GfkFoldClient(C.Structure):
-    """One client's pointers for the fold kernels (csrc/gfk_common.h GfkFoldClient)."""
-    _fields_ = [("tstart", P), ("indices", P), ("values", P), ("nb", P),
-                ("coef", P), ("zn", P), ("thetad", P), ("lse", P), ("s", P), ("rstd", P),
-                ("beta", P), ("beta_m", P), ("beta_v", P), ("dthetad", P), ("dz0", P),
-                ("w_in", P), ("w_in_m", P), ("w_in_v", P), ("flat", P),
-                ("beta_sc", C.c_float), ("win_sc", C.c_float), ("b1", C.c_float), ("b2", C.c_float),
-                ("eps", C.c_float), ("wd", C.c_float),
-                ("wdz", P * FOLD_W), ("wa", P * FOLD_W), ("wp", P * FOLD_W), ("wm", P * FOLD_W),
-                ("wv", P * FOLD_W), ("vsrc", P * FOLD_V), ("vp", P * FOLD_V), ("vm", P * FOLD_V),
-                ("vv", P * FOLD_V), ("vg", P * FOLD_V),
-                ("wsc", C.c_float * FOLD_W), ("vsc", C.c_float * FOLD_V)]
-
-
-class GfkFold(C.Structure):
-    """The in-epilogue FedAvg of a batched launch (csrc/gfk_common.h GfkFold)."""
-    _fields_ = [("models", P), ("upds", P), ("left", P), ("M", C.c_int32), ("mode", C.c_int32),
-                ("n_left", C.c_int32), ("nj", C.c_int32), ("cl", P)]
-
-
-FOLD_ALL, FOLD_FIRST = 0, 1
-
 # optional entry points: name -> (argtypes, restype)
 _EXTRA = {
     "gfk_theta_infer": ([C.POINTER(GfkModel), C.POINTER(GfkInfer), C.c_void_p], C.c_int),
     "gfk_theta_infer_smem": ([C.POINTER(GfkModel)], C.c_size_t),
-    "gfk_bwd_fold_launch": ([C.POINTER(GfkModel), C.POINTER(GfkFold), C.c_void_p], C.c_int),
-    "gfk_win_fold_launch": ([C.POINTER(GfkModel), C.POINTER(GfkUpdate), C.POINTER(GfkFold), C.c_void_p],
-                            C.c_int),
 }
 
 
@@ -323,12 +291,6 @@ def declare(lib: C.CDLL) -> None:
     lib.gfk_thin.restype = C.c_int
     lib.gfk_thin_max_topics.argtypes = []
     lib.gfk_thin_max_topics.restype = C.c_int
-    if hasattr(lib, "gfk_fold_struct_size"):
-        lib.gfk_fold_struct_size.restype = C.c_size_t
-        lib.gfk_fold_client_struct_size.restype = C.c_size_t
-        if (lib.gfk_fold_struct_size() != C.sizeof(GfkFold)
-                or lib.gfk_fold_client_struct_size() != C.sizeof(GfkFoldClient)):
-            raise RuntimeError("GfkFold ABI mismatch")
     for name, args in _EXTRA.items():
         if hasattr(lib, name):
             f = getattr(lib, name)

@@ -18,6 +18,41 @@ def _params(**kw):
     return p
 
 
+def _corpora(n, vocab=5000, docs=None, seed=21, topics=50, frozen=5, nwords=(150, 250)):
+    # uneven shards: different FedAvg weights and different partial last batches
+    sc = generate_synthetic(vocab_size=vocab, n_topics=topics, n_docs=docs or 150 * n, n_nodes=n,
+                            frozen_topics=frozen, nwords=nwords, seed=seed)
+    return [ClientCorpus(synthetic=sc, node=i) for i in range(n)]
+
+
+def _state(fed):
+    out = []
+    for c in fed.clients:
+        e = c.tm.engine
+        out += [c.tm.flat.buffer.clone(), e.exp_avg.clone(), e.exp_avg_sq.clone(),
+                e.loss_hist.clone()]
+    return out
+
+
+def _assert_same(a, b):
+    """Bitwise equality of two runs' states; on a mismatch, name the client, buffer and
+    flat-layout slot of the first differing element."""
+    sa, sb = _state(a), _state(b)
+    for i, (x, y) in enumerate(zip(sa, sb)):
+        if torch.equal(x, y):
+            continue
+        c, kind = divmod(i, 4)
+        j = int(torch.nonzero(x != y)[0])
+        slot = None
+        if kind < 3:
+            for k, s in a.clients[c].tm.flat.slots.items():
+                if s.offset <= j < s.offset + s.numel:
+                    slot = (k, j - s.offset)
+        n = int((x != y).sum())
+        raise AssertionError(f"client {c} {['param', 'exp_avg', 'exp_avg_sq', 'loss'][kind]}: "
+                             f"{n} elements differ, first {j} {slot}: {float(x[j])!r} vs {float(y[j])!r}")
+
+
 @pytest.mark.parametrize("model_type", ["prodLDA", "LDA"])
 def test_fused_federation_round_is_fedavg(model_type):
     sc = generate_synthetic(vocab_size=400, n_topics=10, n_docs=60, n_nodes=3, frozen_topics=2,
@@ -195,7 +230,7 @@ def test_batched_round_matches_branch_round(model_type):
     """One launch per phase for all clients (grid z = client, the kernels' batched
     instances) == one graph branch per client (the by-value instances): after one round
     within fp32 rounding (the two instances are compiled separately, so FMA contraction
-    may differ), and two batched runs are bitwise equal."""
+    may differ)."""
     sc = generate_synthetic(vocab_size=500, n_topics=10, n_docs=70, n_nodes=4, frozen_topics=2,
                             nwords=(30, 60), seed=12)
     corpora = [ClientCorpus(synthetic=sc, node=i) for i in range(4)]
@@ -215,12 +250,41 @@ def test_batched_round_matches_branch_round(model_type):
         assert int((diff > 1e-5).sum()) <= 0.01 * diff.numel()
         torch.testing.assert_close(x.tm.engine.loss_hist[:1], y.tm.engine.loss_hist[:1],
                                    rtol=1e-6, atol=1e-3)
-    c = LocalFederation(corpora, p, max_iters=12, round_batched=True, **kw)
-    d = LocalFederation(corpora, p, max_iters=12, round_batched=True, **kw)
-    c.run()
-    d.run()
-    for x, y in zip(c.clients, d.clients):
-        assert torch.equal(x.tm.flat.buffer, y.tm.flat.buffer)
+
+
+_HEADLINE = dict(batch_size=64, n_components=50)
+
+
+@pytest.mark.parametrize("corpus,params,seed,iters", [
+    pytest.param(dict(n=4, vocab=500, docs=70, seed=12, topics=10, frozen=2, nwords=(30, 60)),
+                 dict(model_type="prodLDA"), 4, 12, id="v500-prodLDA"),
+    pytest.param(dict(n=4, vocab=500, docs=70, seed=12, topics=10, frozen=2, nwords=(30, 60)),
+                 dict(model_type="LDA"), 4, 12, id="v500-LDA"),
+    pytest.param(dict(n=3, docs=500), _HEADLINE, 7, 25, id="3-clients-epochs"),
+    pytest.param(dict(n=4, vocab=3000, docs=600, seed=5), dict(_HEADLINE, learn_priors=True), 7, 12,
+                 id="learn-priors"),
+])
+def test_batched_round_is_bitwise_repeatable(corpus, params, seed, iters):
+    """LocalFederation's batched round (one launch per phase for all clients + the fold
+    kernel) over several epochs -- uneven shards, partial last batches, 3 clients (no power
+    of two), learned priors (vector jobs without a source: the gradient slot): two
+    identically seeded runs end with the same parameters, Adam moments and losses bit for
+    bit, and every client holds client 0's shared state."""
+    corpora = _corpora(**corpus)
+    runs = []
+    for _ in range(2):
+        fed = LocalFederation(corpora, _params(**params), max_iters=iters, device="cuda",
+                              backend="fused", seed=seed, round_batched=True)
+        fed.run()
+        torch.cuda.synchronize()
+        runs.append(fed)
+    a, b = runs
+    assert a._batched is not None and a.fold_plan == b.fold_plan == "fold kernel"
+    _assert_same(a, b)
+    s0 = a.clients[0].shared
+    for c in a.clients:
+        assert torch.equal(c.shared, s0)
+        assert np.isfinite(c.loss_history()[:iters]).all()
 
 
 @pytest.mark.parametrize("strip", ["fill", "keep"])
