@@ -222,6 +222,10 @@ constexpr int GFK_POST_ROWS2 = 1048576;
 // with bits 20 and 21): four rows per workgroup instead of two
 constexpr int GFK_POST_JOINT = 2097152;
 constexpr int GFK_POST_ROWS4 = 4194304;
+// stage_flags bit 23 (GFK_BWD_BATCH8, batched launches): ProdLDA's one-range tile backward as
+// 8-wave workgroups, three per CU, so all clients' tiles are resident at once
+// (csrc/prodlda.hip prodlda_bwd8_kernel: bmax 64, K <= 64, fp32)
+constexpr int GFK_BWD_BATCH8 = 8388608;
 // rows whose own-row vectors post_bwd keeps in LDS at once (1: the serial shapes)
 __host__ __device__ __forceinline__ int gfk_post_joint_rows(int stage_flags) {
   return !(stage_flags & GFK_POST_JOINT) ? 1 : (stage_flags & GFK_POST_ROWS4) ? 4 : 2;
@@ -387,8 +391,19 @@ namespace gfk {
       (m).dbg[slot] = __builtin_amdgcn_s_memtime();                               \
     __builtin_amdgcn_sched_barrier(0);                                            \
   } while (0)
+// ... thread 0 of every workgroup where `cond` holds (a batched launch: the clients whose
+// descriptor carries dbg), in s_memrealtime ticks (100 MHz, one counter for the whole chip:
+// s_memtime of two CUs cannot be compared)
+#define GFK_STAMP_IF(m, cond, slot)                                               \
+  do {                                                                            \
+    __builtin_amdgcn_sched_barrier(0);                                            \
+    if ((cond) && threadIdx.x == 0 && (m).dbg)                                    \
+      (m).dbg[slot] = __builtin_amdgcn_s_memrealtime();                           \
+    __builtin_amdgcn_sched_barrier(0);                                            \
+  } while (0)
 #else
 #define GFK_STAMP(m, slot) do { } while (0)
+#define GFK_STAMP_IF(m, cond, slot) do { } while (0)
 #endif
 
 // Philox4x32-10 counter-based RNG: stateless, so every kernel (and every graph

@@ -1543,6 +1543,9 @@ __global__ void __launch_bounds__(64 * NW) prodlda_lb_bwd_kernel(GfkArgT<false> 
 // accumulators stay in registers).
 __host__ __device__ __forceinline__ int kt_stride(int w) { return w % 32 == 16 ? w : w + 16; }
 __host__ __device__ __forceinline__ int bwd_kpq(int K, int kq) { return 16 * ((round_up(K, 16) / 16 + kq - 1) / kq); }
+// the 8-wave tile backward (stage_flags GFK_BWD_BATCH8): floats of the region that holds the
+// logit tile [B][VB] and after it the beta block [KPQ][LDB_B]
+__host__ __device__ __forceinline__ int bwd_zb(int B, int KPQ) { return B * VB > KPQ * LDB_B ? B * VB : KPQ * LDB_B; }
 // bwd_pre = 3 runs the software-pipelined backward (fp32, B = 64; else the bwd_pre = 2 one),
 // whose dlogit tiles are dense [B][64]
 // (its buffer-descriptor stores need beta's rows padded to whole 64-column tiles and the
@@ -1645,10 +1648,20 @@ __global__ void __launch_bounds__(256) prodlda_dlogit_kernel(GfkArgT<GB> ga) {
 // swizzle a per-lane constant) + bt + dt, and the dbeta tile G reuses dt's space (one
 // extra barrier): ~50 KB at B = 64, K = 200, so THREE workgroups share a CU (24 waves)
 // instead of two.
-template <int BM, int MAXU, int KQ, bool BF, bool PRE, bool OWN = false>
+// NT (KQ = 1 only; 0: the 16-wave workgroup): the 8-wave tile backward of the batched
+// headline (stage_flags GFK_BWD_BATCH8).  Three workgroups share a CU (80 VGPRs, a third of
+// the LDS), so M clients' tiles are all resident where two 16-wave workgroups per CU leave a
+// second round.  Its LDS is th + one region for the logit tile and then the beta block
+// (the beta block waits in registers through the sparse and dense passes) + dt, which the
+// G tile reuses (through registers and one barrier, as PRE does) + lse / S / rstd; the
+// row-wise Adam state is loaded after both MFMA blocks.  Every output element keeps the
+// 16-wave instance's arithmetic: only the wave or thread that computes it changes.
+template <int BM, int MAXU, int KQ, bool BF, bool PRE, bool OWN = false, int NT = 0>
 __device__ __forceinline__ void prodlda_bwd_body(const GfkModel& m) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  constexpr int NTH = KQ == 1 ? DEC_THREADS : 512;
+  constexpr int NTH = NT ? NT : KQ == 1 ? DEC_THREADS : 512;
+  constexpr bool CL = NT != 0;                 // the compact LDS layout above
+  static_assert(!CL || (KQ == 1 && !PRE && !BF && NT == 512 && BM == 64 && MAXU == 1), "8-wave tile backward");
   // KQ = 1 with more than 3 k tiles only ever runs with one tile per workgroup (the
   // persistent shape of such K is KQ = 4): no tile loop, no loop-carried registers
   constexpr bool SINGLE = KQ == 1 && MAXU >= 2;
@@ -1679,8 +1692,8 @@ __device__ __forceinline__ void prodlda_bwd_body(const GfkModel& m) {
   const int KPQ = bwd_kpq(K, KQ), KTQ = PRE ? 64 : KQ == 1 ? m.kt : kt_stride(KPQ);
   float* th = smem;
   float* bt = th + BM * KTQ;
-  float* zt = bt + KPQ * LDB_B;                 // PRE: no logit tile; the G tile aliases dt
-  float* dt = PRE ? zt : zt + BM * VB;
+  float* zt = CL ? bt : bt + KPQ * LDB_B;       // PRE: no logit tile; the G tile aliases dt
+  float* dt = PRE ? zt : CL ? zt + bwd_zb(BM, KPQ) : zt + BM * VB;
   float* lse = dt + BM * LDD;
   float* Sb = lse + BM;
   float* rs = Sb + BM;
@@ -1692,6 +1705,13 @@ __device__ __forceinline__ void prodlda_bwd_body(const GfkModel& m) {
   const bool beta_shared = is_shared(m, m.beta);
 
   GFK_STAMP(m, 24);
+  // batched launches (tools/stamps.py --clients): the first-tile and the last-tile workgroup,
+  // slots 600 / 608 + entry, staged, dense done, end
+#ifdef GFK_STAMPS
+  const bool stamp2 = m.n_batch > 1 && KQ == 1 && (slab == 0 || slab == nslab - 1);
+  const int slot2 = slab == 0 ? 600 : 608;
+#endif
+  GFK_STAMP_IF(m, stamp2, slot2);
   // ---- once per workgroup: theta_d columns [kb, kb + 16 nks), lse, S ----
   if (KQ == 1) {
     glds_copy(th, m.ws_thetad, BM * m.kt, tid, NTH);           // KTQ == kt for one range
@@ -1770,14 +1790,14 @@ __device__ __forceinline__ void prodlda_bwd_body(const GfkModel& m) {
     const int c = tile * VB + (tid & (VB - 1));
     return c < V ? c * 4 : 0x7FFF0000;
   };
-  auto issue_state_rw = [&](int tile) {
+  auto issue_state_rw = [&](int tile, float (&sm_)[RU], float (&sv_)[RU]) {
     const int vcol = rw_col(tile);
 #pragma unroll
     for (int u = 0; u < RU; ++u) {
       const int k = min(kb + tid / VB + RPU * u, K - 1);
       const int vo = boff(vcol, k * m.ldb * 4);
-      rm_[u] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_m, vo, 0, 0));
-      rv_[u] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_v, vo, 0, 0));
+      sm_[u] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_m, vo, 0, 0));
+      sv_[u] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_v, vo, 0, 0));
     }
   };
   // this workgroup's d theta_d partial, per lane (summed over its tiles in order)
@@ -1800,8 +1820,8 @@ __device__ __forceinline__ void prodlda_bwd_body(const GfkModel& m) {
     // one staging round per tile: every global read is issued before the barrier
     issue_tile(tile);
     if (!PRE) issue_first_nz();
-    if (fused) {
-      if constexpr (RW) issue_state_rw(tile);
+    if (fused && !CL) {
+      if constexpr (RW) issue_state_rw(tile, rm_, rv_);
       else issue_state(tile);
     }
     if (tile != slab) lds_barrier();           // the previous tile's LDS reads are done
@@ -1809,7 +1829,7 @@ __device__ __forceinline__ void prodlda_bwd_body(const GfkModel& m) {
     //      registers -> LDS; zero the logit-gradient tile ----
     if (PRE) glds_copy(dt, m.ws_dt + (size_t)tile * BM * LDD, BM * LDD, tid, NTH);
     else glds_copy(zt, m.ws_zn + (size_t)tile * BM * VB, BM * VB, tid, NTH);
-    {
+    if constexpr (!CL) {
       const int c = tid & (VB - 1), cok = c0 + c < V;
 #pragma unroll
       for (int u = 0; u < BU; ++u) {
@@ -1830,6 +1850,7 @@ __device__ __forceinline__ void prodlda_bwd_body(const GfkModel& m) {
     // the Adam state waits on the epilogue's own stores (vmcnt counts stores too)
     __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0) expcnt(7) lgkmcnt(15)
     GFK_STAMP(m, 25);
+    GFK_STAMP_IF(m, stamp2, slot2 + 1);
 
     // ---- (3) sparse term: dt[b, c] = -x p / (p + 1e-10) at this tile's non-zeros ----
     if (!PRE) {
@@ -1872,6 +1893,16 @@ __device__ __forceinline__ void prodlda_bwd_body(const GfkModel& m) {
     lds_barrier();
     }  // !PRE
     GFK_STAMP(m, 27);
+    GFK_STAMP_IF(m, stamp2, slot2 + 2);
+    if constexpr (CL) {         // the logit tile is done: its region takes the beta block
+      const int c = tid & (VB - 1), cok = c0 + c < V;
+#pragma unroll
+      for (int u = 0; u < BU; ++u) {
+        const int k = tid / VB + RPU * u;
+        if (k < 16 * nks) bt[k * LDB_B + c] = (kb + k < K && cok) ? br[u] : 0.f;
+      }
+      lds_barrier();
+    }
 
     // ---- (5) d theta_d[b, k] += sum_c dlogit[b, c] beta[k, c] over the k range ----
     auto dtheta_tile = [&]() {
@@ -1983,7 +2014,7 @@ __device__ __forceinline__ void prodlda_bwd_body(const GfkModel& m) {
 #pragma unroll                    // half-wave's 2 rows x 16 columns hit 32 distinct banks
           for (int e = 0; e < 4; ++e) {
             const int kl = ks * 16 + (lane >> 4) * 4 + e;
-            if (PRE) gr[u][e] = a0[e] + a1[e];    // (G aliases dt: stored after a barrier)
+            if (PRE || CL) gr[u][e] = a0[e] + a1[e];    // (G aliases dt: stored after a barrier)
             else zt[kl * VB + (cl ^ ((kl & 4) << 2))] = a0[e] + a1[e];
           }
           continue;
@@ -2025,11 +2056,16 @@ __device__ __forceinline__ void prodlda_bwd_body(const GfkModel& m) {
         }
       }
     };
-    if (PRE && RW) {
+    float tm_[RU] = {}, tv_[RU] = {};          // (CL) this tile's row-wise Adam state
+    if ((PRE || CL) && RW) {
       // d theta_d first, then dbeta into registers; every wave is done reading dt before
       // the G tile overwrites it
       dtheta_tile();
       dbeta_tile();
+      // (CL) the Adam state behind both MFMA blocks, in registers of this tile's own (rm_ /
+      // rv_ live across the tile loop): under them it does not fit 80 VGPRs.  The two
+      // barriers of the G tile and the CU's other workgroups cover the loads.
+      if constexpr (CL) if (fused) issue_state_rw(tile, tm_, tv_);
       lds_barrier();
 #pragma unroll
       for (int u = 0; u < MU; ++u) {
@@ -2039,7 +2075,7 @@ __device__ __forceinline__ void prodlda_bwd_body(const GfkModel& m) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int kl = ks * 16 + (lane >> 4) * 4 + e;
-          zt[kl * VB + (cl ^ ((kl & 4) << 2))] = gr[u][e];
+          (CL ? dt : zt)[kl * VB + (cl ^ ((kl & 4) << 2))] = gr[u][e];
         }
       }
     } else {
@@ -2058,12 +2094,12 @@ __device__ __forceinline__ void prodlda_bwd_body(const GfkModel& m) {
       for (int u = 0; u < RU; ++u) {
         const int kl = kl0 + RPU * u, k = kb + kl;
         if (kl >= 16 * nks || k >= K) continue;   // (wave-uniform)
-        const float g = zt[kl * VB + cs];
+        const float g = (CL ? dt : zt)[kl * VB + cs];   // the G tile
         const int off = boff(vcol, k * m.ldb * 4);
         if (!fused) {
           __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(g), rs_g, off, 0, 0);
         } else {
-          float mo = rm_[u], vo = rv_[u];
+          float mo = CL ? tm_[u] : rm_[u], vo = CL ? tv_[u] : rv_[u];
           float np = adam_update(bt[kl * LDB_B + cl], g, mo, vo, ac);
           if (beta_shared && m.fed_scale_on) np *= m.fed_scale;
           __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(mo), rs_m, off, 0, 0);
@@ -2073,6 +2109,7 @@ __device__ __forceinline__ void prodlda_bwd_body(const GfkModel& m) {
       }
     }
     GFK_STAMP(m, 28);
+    GFK_STAMP_IF(m, stamp2, slot2 + 3);
     if (SINGLE) break;
   }
   // ---- this workgroup's d theta_d partial (plain stores; row_bwd sums the slabs in order) ----
@@ -2096,6 +2133,15 @@ __global__ void __launch_bounds__(KQ == 1 ? DEC_THREADS : 512, KQ == 1 ? 1 : 2)
 prodlda_bwd_kernel(GfkArgT<GB> ga) {
   const GfkModel& m = gfk_model(ga);
   prodlda_bwd_body<BM, MAXU, KQ, BF, false, GB>(m);
+}
+
+// stage_flags GFK_BWD_BATCH8: the one-range tile backward in 8 waves (B = 64, K <= 64, fp32),
+// three workgroups per CU: 80 VGPRs and at most a third of the LDS (bwd8_ok)
+template <int BM, int MAXU, bool GB = false>
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6)))
+prodlda_bwd8_kernel(GfkArgT<GB> ga) {
+  const GfkModel& m = gfk_model(ga);
+  prodlda_bwd_body<BM, MAXU, 1, false, false, GB, 512>(m);
 }
 
 // the precomputed-dlogit shape (bwd_pre = 2): the compiler's register budget, two 8-wave
@@ -2444,8 +2490,21 @@ __host__ __device__ inline int bwd_kq(const GfkModel& m) {
   return (m.n_dpart < m.n_tiles && round_up(m.K, 16) / 16 >= 4) ? 4 : 1;
 }
 
+// the LDS a CU's three 8-wave workgroups may take each (160 KB per CU)
+constexpr size_t BWD8_LDS = 160 * 1024 / 3;
+static size_t bwd8_smem(const GfkModel* m) {
+  const size_t B = m->bmax;
+  return sizeof(float) * (B * m->kt + bwd_zb((int)B, bwd_kpq(m->K, 1)) + B * LDD + 2 * B + VB);
+}
+// whether the 8-wave tile backward (GFK_BWD_BATCH8) has an instance for this model
+static bool bwd8_ok(const GfkModel* m) {
+  return bwd_kq(*m) == 1 && !m->bwd_pre && m->bmax == 64 && m->K <= 64 && !m->mm_bf16 &&
+         bwd8_smem(m) <= BWD8_LDS;
+}
+
 static size_t bwd_smem(const GfkModel* m, int kq) {
   const size_t KPQ = bwd_kpq(m->K, kq), B = m->bmax;
+  if (kq == 1 && (m->stage_flags & GFK_BWD_BATCH8)) return bwd8_smem(m);
   if (kq == 4 && bwd_pipe(*m)) return sizeof(float) * 4 * 64 * 72;   // thT, bt, dt, dtT
   if (kq == 4 && m->bwd_pre && B <= 64)       // th [B][64] + bt + dt (G aliases dt)
     return sizeof(float) * (B * 64 + KPQ * LDB_B + B * LDD);
@@ -2488,7 +2547,8 @@ static const GfkRow kFwdStrip[] = {STRIP_ROWS(16), STRIP_ROWS(32), STRIP_ROWS(64
 // backward: {kernel, bmax, 64-topic units (K + 63) / 64, flag}.  kernel: the tile backward
 // by its k ranges (1 / 4; flag = bf16), the k-range backward reading the stored logit
 // gradient (pre2; flag = bf16), the pipelined one (flag = fused update, bmax 64 only)
-enum { BWD_PRE2 = 2, BWD_PIPE = 3 };    // (1, 4: the tile backward's KQ)
+// the 8-wave one-range tile backward (BWD_W8; bmax 64, one unit, fp32 only)
+enum { BWD_PRE2 = 2, BWD_PIPE = 3, BWD_W8 = 8 };    // (1, 4: the tile backward's KQ)
 #define BWD_ROWS_B(BM, U, BF)                                          \
   {{1, BM, U, BF}, GFK_PAIR(prodlda_bwd_kernel, BM, U, 1, BF)},        \
   {{4, BM, U, BF}, GFK_PAIR(prodlda_bwd_kernel, BM, U, 4, BF)}
@@ -2498,7 +2558,8 @@ enum { BWD_PRE2 = 2, BWD_PIPE = 3 };    // (1, 4: the tile backward's KQ)
   BWD_ROWS_P(16, U, BF), BWD_ROWS_P(32, U, BF), BWD_ROWS_P(64, U, BF),                            \
   {{BWD_PIPE, 64, U, BF}, GFK_PAIR(prodlda_bwd_pipe_kernel, 64, U, BF)}
 #define BWD_ROWS(U) BWD_ROWS_F(U, false), BWD_ROWS_F(U, true)
-static const GfkRow kBwd[] = {BWD_ROWS(1), BWD_ROWS(2), BWD_ROWS(3), BWD_ROWS(4)};
+static const GfkRow kBwd[] = {BWD_ROWS(1), BWD_ROWS(2), BWD_ROWS(3), BWD_ROWS(4),
+                              {{BWD_W8, 64, 1, false}, GFK_PAIR(prodlda_bwd8_kernel, 64, 1)}};
 #undef BWD_ROWS
 #undef BWD_ROWS_F
 #undef BWD_ROWS_P
@@ -2573,6 +2634,10 @@ extern "C" int gfk_launch_prodlda_bwd(const GfkModel* m, hipStream_t s) {
   const size_t sm = bwd_smem(m, kq);
   const dim3 g(kq == 4 ? 4 * slabs : slabs), blk(kq == 1 ? DEC_THREADS : 512);
   const bool bf = m->mm_bf16;
+  if (m->stage_flags & GFK_BWD_BATCH8) {             // (no instance: an error, never the 16-wave shape)
+    if (!bwd8_ok(m)) return -1;
+    return gfk_launch(gfk_find(kBwd, BWD_W8, m->bmax, maxu, false), m, g, dim3(512), sm, s);
+  }
   if (kq == 4 && m->bwd_pre && m->bmax <= 64) {      // (static LDS: B <= 64)
     const int e = gfk_launch(gfk_find(kDlogit, m->bmax), m, dim3(m->n_tiles), dim3(256), 0, s);
     if (e) return e;

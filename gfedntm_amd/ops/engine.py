@@ -71,6 +71,9 @@ STAGE_POST_ROWS2 = abi.POST_ROWS2  # bit 20: batched post_bwd, two rows per work
                                    #         workgroup in row_bwd (csrc/posterior.hip)
 STAGE_POST_JOINT = abi.POST_JOINT  # bit 21: ... the rows through each phase together (with bit 20)
 STAGE_POST_ROWS4 = abi.POST_ROWS4  # bit 22: ... four rows per workgroup (with bits 20 and 21)
+STAGE_BWD_BATCH8 = abi.BWD_BATCH8  # bit 23: batched ProdLDA tile backward, 8-wave workgroups, three per CU
+# the LDS one of a CU's three 8-wave backward workgroups may take (csrc/prodlda.hip BWD8_LDS)
+BWD8_LDS = LDS_LIMIT // 3
 # the shape GFEDNTM_POST_ROWS=auto takes where bit 20 applies (a key of abi.POST_ROWS_SHAPES):
 # the headline's interleaved A/B, 8 clients K = 50 (profiles/r7/ab_post_rows.txt): serial2
 # 0.1176 ms per round, two joint rows 0.1159, four 0.1193
@@ -94,6 +97,42 @@ def post_rows_flags(n_clients: int, bmax: int, cus: int, knob: str = "auto") -> 
     if knob not in abi.POST_ROWS_SHAPES:
         raise ValueError(f"GFEDNTM_POST_ROWS={knob!r}: expected auto, serial2, 2 or 4")
     return abi.POST_ROWS_SHAPES[knob]
+
+
+def bwd_kq(n_tiles: int, n_dpart: int, K: int) -> int:
+    """k ranges of ProdLDA's tile backward (csrc/prodlda.hip bwd_kq)."""
+    return 4 if n_dpart < n_tiles and -(-K // 16) >= 4 else 1
+
+
+def bwd8_lds_bytes(bmax: int, K: int, kt: int) -> int:
+    """Dynamic LDS of the 8-wave tile backward (csrc/prodlda.hip bwd8_smem): theta_d, the
+    region of the logit tile and then the beta block, the logit gradient, lse / S / rstd."""
+    kpq = -(-K // 16) * 16
+    return 4 * (bmax * kt + max(bmax * VB, kpq * 66) + bmax * 66 + 2 * bmax + VB)
+
+
+def bwd_batch8_flag(n_clients: int, n_tiles: int, cus: int, *, bmax: int, K: int, bf16: bool,
+                    kq: int, bwd_pre: int, lds_bytes: int, knob: str = "auto") -> int:
+    """stage_flags bit of a batched launch's ProdLDA tile backward (GFEDNTM_BWD_WAVES).
+
+    The 8-wave instance exists for the one-range tile backward (``kq`` = 1 -- 0 where the
+    model runs no tile backward at all --, no precomputed logit gradient) at bmax = 64,
+    K <= 64, fp32, within a third of a CU's LDS.  ``auto``: where M clients' tiles are more
+    than two 16-wave workgroups per CU hold at once and at most the three 8-wave ones do
+    (2 CUs < M n_tiles <= 3 CUs: one round instead of two).  ``8`` / ``16`` force the shape
+    on every launch of M > 1 clients; ``8`` without an instance is an error."""
+    if knob not in ("auto", "16", "8"):
+        raise ValueError(f"GFEDNTM_BWD_WAVES={knob!r}: expected auto, 16 or 8")
+    if n_clients < 2 or knob == "16":
+        return 0
+    exists = (kq == 1 and not bwd_pre and bmax == 64 and K <= 64 and not bf16
+              and lds_bytes <= BWD8_LDS)
+    if knob == "8":
+        if not exists:
+            raise RuntimeError("GFEDNTM_BWD_WAVES=8: no 8-wave tile backward for this launch "
+                               "(one-range fp32 tile backward, bmax 64, K <= 64, LDS <= %d B)" % BWD8_LDS)
+        return STAGE_BWD_BATCH8
+    return STAGE_BWD_BATCH8 if exists and 2 * cus < n_clients * n_tiles <= 3 * cus else 0
 
 
 def engine_bmax(tm) -> int:
@@ -1791,6 +1830,16 @@ class BatchedSteps:
             # they exceed two rounds of 16-wave workgroups
             if M * (mm.n_tiles + 8) > 2 * self._cu:
                 mm.stage_flags |= STAGE_WIN_BATCH8
+            # prodlda_bwd: two 16-wave workgroups share a CU, so 8 clients x 74 tiles run as
+            # a round of 64 tiles per XCD and a second one of 10; three 8-wave workgroups
+            # per CU hold them all at once.  GFEDNTM_BWD_WAVES = auto | 16 | 8
+            tile_bwd = (mm.kind == abi.KIND_PRODLDA and not mm.stage_flags & STAGE_LB
+                        and abi.PH_PRODLDA_BWD in self.engines[0].phases())
+            mm.stage_flags |= bwd_batch8_flag(
+                M, mm.n_tiles, self._cu, bmax=mm.bmax, K=mm.K, bf16=bool(mm.mm_bf16),
+                kq=bwd_kq(mm.n_tiles, mm.n_dpart, mm.K) if tile_bwd else 0, bwd_pre=mm.bwd_pre,
+                lds_bytes=bwd8_lds_bytes(mm.bmax, mm.K, mm.kt),
+                knob=os.environ.get("GFEDNTM_BWD_WAVES", "auto"))
             uu = e._u
             if self._shared is not None:
                 uu = abi.GfkUpdate.from_buffer_copy(bytes(e._u))
@@ -1814,6 +1863,13 @@ class BatchedSteps:
             self._arr_u.copy_(torch.frombuffer(bytearray(b"".join(us)), dtype=torch.uint8))
             self._blob = blob
         self._host = abi.GfkModel.from_buffer_copy(ms[0])
+        # the shapes this launch runs, for records: "8 clients per launch; prodlda_bwd 8 waves"
+        self.plan = "%d clients per launch" % M
+        if abi.PH_PRODLDA_BWD in ph and not self._host.stage_flags & STAGE_LB:
+            self.plan += "; prodlda_bwd " + (
+                "8 waves" if self._host.stage_flags & STAGE_BWD_BATCH8 else
+                "16 waves" if bwd_kq(self._host.n_tiles, self._host.n_dpart, self._host.K) == 1
+                else "k ranges")
 
     def prepare(self):
         """Upload the descriptors now (before a capture)."""

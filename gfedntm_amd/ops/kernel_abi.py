@@ -27,6 +27,10 @@ POST_ROWS4 = 1 << 22
 POST_ROWS_SHAPES = {"serial2": POST_ROWS2, "2": POST_ROWS2 | POST_JOINT,
                     "4": POST_ROWS2 | POST_JOINT | POST_ROWS4}
 
+# stage_flags bit of the batched ProdLDA tile backward in 8-wave workgroups (csrc/gfk_common.h
+# GFK_BWD_BATCH8; ops/engine.py bwd_batch8_flag)
+BWD_BATCH8 = 1 << 23
+
 # phase ids (csrc/step.cpp GfkPhase)
 PH_BATCH_DOCS = 0
 PH_ENC_FWD = 1

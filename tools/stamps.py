@@ -9,8 +9,14 @@ absolute length (the stamps add fences).
 (python tools/stamps.py --build-only on the CPU host, then --so build/stamps/... copied
 to a travelling path on the GPU box, so the box does not compile)
 
+--clients M (M > 1): M such models through ops/engine.py BatchedSteps, one launch per phase
+with grid z = the clients.  Client 0 alone carries the stamp buffer; of its decoder backward
+the first-tile and the last-tile workgroup are stamped (entry, staged, dense done, end), which
+shows whether the last tiles wait for a second round of workgroups (GFEDNTM_BWD_WAVES picks
+the backward's shape).
+
 usage: python tools/stamps.py [--topics K] [--vocab V] [--hidden 50,50] [--batch B]
-                              [--nnz N] [--docs D] [--steps S]
+                              [--nnz N] [--docs D] [--steps S] [--clients M]
 """
 import argparse
 import os
@@ -40,6 +46,44 @@ def build():
     return so
 
 
+def batched(a, kw):
+    """M clients' steps as batched launches; the decoder backward's first-tile and last-tile
+    workgroups of client 0 (csrc/prodlda.hip, dbg slots 600 / 608 + entry, staged, dense
+    done, end)."""
+    import torch
+    from gfedntm_amd.data.bow import BatchPlan, DeviceCSR
+    from gfedntm_amd.models import AVITM
+    from gfedntm_amd.ops.engine import BatchedSteps
+    from tests.helpers import random_csr
+    tms = []
+    for i in range(a.clients):
+        tm = AVITM(**kw)
+        tm.engine.bind_data(DeviceCSR(random_csr(a.docs, a.vocab, a.nnz, seed=i), "cuda"),
+                            BatchPlan.build(a.docs, a.batch, a.steps))
+        tms.append(tm)
+    dbg = torch.zeros(1024, dtype=torch.int64, device="cuda")
+    tms[0].engine._m.dbg = dbg.data_ptr()
+    bs = BatchedSteps([t.engine for t in tms])
+    bs.prepare()
+    rows = []
+    for s in range(a.steps):
+        dbg.zero_()
+        bs.launch()
+        torch.cuda.synchronize()
+        rows.append(dbg[600:616].cpu().numpy().reshape(2, 8)[:, :4].copy())
+    m = bs._host
+    print(f"clients={a.clients} K={a.topics} V={a.vocab} tiles={m.n_tiles} n_dpart={m.n_dpart} "
+          f"stage_flags={m.stage_flags} plan: {bs.plan}")
+    print("prodlda_bwd, client 0, microseconds (s_memrealtime, 10 ns ticks) from the first-tile "
+          "workgroup's entry: entry, staged, dense done, end")
+    for s, r in enumerate(rows):
+        if s < a.steps - 5:          # the last five steps (the first ones are cold)
+            continue
+        t0 = r[0, 0]
+        print(f"  step {s}: first tile " + " ".join("%.2f" % ((int(v) - int(t0)) / 100) for v in r[0]) +
+              " | last tile " + " ".join("%.2f" % ((int(v) - int(t0)) / 100) for v in r[1]))
+
+
 def main(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--topics", type=int, default=50)
@@ -51,6 +95,7 @@ def main(argv=None):
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--ctx", type=int, default=0, help="contextual size: CombinedTM when > 0")
     p.add_argument("--bf16", action="store_true", help="matmul_dtype='bf16' (contextual GEMMs)")
+    p.add_argument("--clients", type=int, default=1, help="M > 1: the batched launch of M clients")
     p.add_argument("--so", default=None, help="a prebuilt -DGFK_STAMPS library (--build-only)")
     p.add_argument("--build-only", action="store_true", help="build it on the host and stop")
     a = p.parse_args(argv)
@@ -70,6 +115,8 @@ def main(argv=None):
               verbose=False, backend="fused", device="cuda")
     if a.bf16:
         kw["matmul_dtype"] = "bf16"
+    if a.clients > 1:
+        return batched(a, kw)
     tm = CombinedTM(contextual_size=a.ctx, **kw) if a.ctx else AVITM(**kw)
     X = random_csr(a.docs, a.vocab, a.nnz, seed=0)
     ctx = (np.random.default_rng(1).standard_normal((a.docs, a.ctx)).astype(np.float32)
