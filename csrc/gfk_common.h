@@ -178,6 +178,10 @@ typedef struct GfkModel {
   // CombinedTM backward, persistent pipelined shape (stage_flags bit 12): workgroups
   // (one per CU) of csrc/ctx.hip gfk_ctx_bwd_pp_k (0: the (tile, chunk) grid)
   int32_t ctx_bgrid;
+  // row stride of epoch_loss in floats (below; here, in the padding before the next pointer,
+  // so the epoch fields end in the descriptor's last 64-byte line instead of opening a new one
+  // that every workgroup of the two writer kernels would fetch)
+  int32_t epoch_stride;
   // ---- the large-batch plan (stage_flags GFK_LB): the posterior's column statistics,
   // computed once per step (csrc/posterior.hip gfk_post_colstats_lb_k): [mean | rstd] of the
   // raw heads, [sum dy | sum dy xhat] of the backward, the priors' sums, 2K floats each ----
@@ -194,6 +198,16 @@ typedef struct GfkModel {
   // off_own), so the Adam moments and the gradient slot stay the client's.  0: p is the
   // client's own buffer.  Read by the batched (GB) instances only: gfk_own
   int64_t off_own;
+  // ---- running epoch loss sums (federation/client.py's epoch summaries): the thread that
+  // writes loss_hist[step] also keeps the fp32 left fold of the epoch's losses in step order,
+  //   cum = (step starts an epoch) ? l : *epoch_run + l;  *epoch_run = cum;
+  //   epoch_loss[epoch_idx[step] * epoch_stride] = cum,
+  // so an epoch's slot is final once its last step has run, however many steps a graph replay
+  // carries.  epoch_idx: [n_steps], the epoch of every plan step (a step starts an epoch when
+  // it is step 0 or its predecessor's index differs).  All null: nothing is read or written
+  const int32_t* epoch_idx;
+  float* epoch_run;              // [1] the running sum (cleared by the host on a step jump)
+  float* epoch_loss;             // slot of epoch e at epoch_loss[e * epoch_stride]
 } GfkModel;
 
 // stage_flags bit 16 (GFK_FWD_POSTFOLD): the ProdLDA strip forward's ring variant computes

@@ -504,14 +504,39 @@ __device__ __forceinline__ void post_term_hist(const GfkModel& m, int nb, int st
   }
 }
 
+// The fp32 left fold of the epoch's step losses (GfkModel.epoch_loss), by the thread that wrote
+// loss_hist[step0] = l: run is *epoch_run, ecur / eprev the epoch indices of step0 and of the
+// step before it, loaded early by the caller.
+__device__ __forceinline__ void post_epoch_sum(const GfkModel& m, int step0, int ecur, int eprev,
+                                               float run, float l) {
+  // (first use of the three loaded values: without it the compiler compares the two indices
+  // right behind their loads and waits a round trip there, in the middle of the workgroup)
+  asm volatile("" : "+v"(ecur), "+v"(eprev), "+v"(run));
+  const float cum = (step0 == 0 || eprev != ecur) ? l : run + l;
+  *m.epoch_run = cum;
+  m.epoch_loss[(int64_t)ecur * m.epoch_stride] = cum;
+}
+
 __device__ __forceinline__ void post_batch_level(const GfkModel& m, int nb, float* scratch, int tid) {
   __shared__ float red[3 * PT];
   const int K = m.K;
   const float wk = m.kl_weight;
   const int step0 = *m.step;
+  // the epoch's running loss sum (GfkModel.epoch_loss): the running sum with the first loads
+  const bool esum = m.epoch_loss != nullptr;
+  float erun = 0.f;
+  int ecur = 0, eprev = 0;
+  if (esum && tid == 0) erun = *m.epoch_run;
   float lterm = 0.f;
   for (int b = tid; b < nb; b += PT)
     lterm += wk * m.ws_kl[b] + m.ws_rl[b] + (m.lab_on ? m.ws_ce[b] : 0.f);
+  // (the epoch indices only here: they need step0, and issued before the loss terms' loads
+  // they held every later load back for the step counter's round trip; they land under the
+  // priors' sums)
+  if (esum && tid == 0) {
+    ecur = m.epoch_idx[step0];
+    eprev = m.epoch_idx[max(step0 - 1, 0)];
+  }
   if (m.learn_priors) {
     constexpr int RB = 16;
     const int cw = K <= 64 ? 64 : K <= 128 ? 128 : PT, ng = PT / cw;
@@ -557,6 +582,7 @@ __device__ __forceinline__ void post_batch_level(const GfkModel& m, int nb, floa
   const float l = block_sum_wave0(lterm, scratch);
   if (tid == 0) {
     m.loss_hist[step0] = l;
+    if (esum) post_epoch_sum(m, step0, ecur, eprev, erun, l);
     *m.step = step0 + 1;
   }
   if (m.kl_hist) post_term_hist(m, nb, step0, scratch, tid, PT);
@@ -941,6 +967,17 @@ __global__ void __launch_bounds__(FT) gfk_post_bwd_k(GfkArgT<GB> ga) {
   const float inv_nb = 1.f / (float)nb;
   if (extra) {
     // ---- extra workgroup: prior gradients (-> grad slots), loss, step ----
+    // the epoch's running loss sum (GfkModel.epoch_loss): step0 is known, thread 0's loads
+    // are in flight under the priors' sums.  (Values of this branch alone: held from the
+    // kernel's first loads on they cost the row workgroups registers)
+    const bool esum = m.epoch_loss != nullptr;
+    float erun = 0.f;
+    int ecur = 0, eprev = 0;
+    if (esum && tid == 0) {
+      erun = *m.epoch_run;
+      ecur = m.epoch_idx[step0];
+      eprev = m.epoch_idx[max(step0 - 1, 0)];
+    }
     const float* pmean = smem + L.pm;   // prior mean, staged
     if constexpr (in_lds) {             // LDS: 16 lanes per column, DPP reductions
       for (int cb = 0; cb < 2 * K; cb += FT / 16) {
@@ -986,6 +1023,7 @@ __global__ void __launch_bounds__(FT) gfk_post_bwd_k(GfkArgT<GB> ga) {
     const float l = block_sum_wave0(lterm, smem + L.red);
     if (tid == 0) {
       m.loss_hist[step0] = l;
+      if (esum) post_epoch_sum(m, step0, ecur, eprev, erun, l);
       *m.step = step0 + 1;
     }
     if (m.kl_hist) post_term_hist(m, nb, step0, smem + L.red, tid, FT);

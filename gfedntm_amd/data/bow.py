@@ -198,6 +198,17 @@ class BatchPlan:
         return self.order[self.start[step]: self.start[step] + self.size[step]]
 
 
+def epoch_index(epoch_end: np.ndarray) -> np.ndarray:
+    """The epoch of every plan step, int32 [n_steps]: the number of epoch ends before it
+    (step s starts an epoch when s == 0 or ``epoch_end[s - 1]``).  A pure function of
+    ``BatchPlan.epoch_end``; ``out[-1] + 1`` epochs are touched, the last maybe incomplete."""
+    end = np.asarray(epoch_end, dtype=bool)
+    out = np.zeros(len(end), dtype=np.int32)
+    if len(end) > 1:
+        out[1:] = np.cumsum(end[:-1], dtype=np.int64)
+    return out
+
+
 def corpus_from_texts(texts: Sequence[str], vocabulary: Dict[str, int]) -> sp.csr_matrix:
     from .vocab import vectorize
     return vectorize(texts, vocabulary)

@@ -22,9 +22,11 @@ identical -- and the batch-norm running statistics are averaged separately
 Differences by design: the per-minibatch loss line needs the loss on the host,
 which would force a device sync every round, so it is logged every
 ``log_every`` rounds (0 = never).  The epoch summary never stalls the device:
-at an epoch end the epoch's loss sum is reduced on device and copied into
-pinned host memory behind an event; the line is emitted (with the reference
-arithmetic) by :meth:`poll` once the event has completed, or by :meth:`flush`.  The results are saved once when
+the epoch's loss sum is kept by the step kernels in a device slot (federation/
+epoch_sums.py; or reduced on device at the epoch end, GFEDNTM_EPOCH_SUMS=host, the
+torch backend) and copied into pinned host memory behind an event; the line is
+emitted (with the reference arithmetic) by :meth:`poll` once the event has
+completed, or by :meth:`flush`.  The results are saved once when
 ``num_epochs`` is reached (the reference re-runs inference and re-saves on every
 later round, B16) and, optionally, the client stops (``stop_at_num_epochs``).
 """
@@ -37,11 +39,13 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from ..data.bow import BatchPlan
+from ..data.bow import BatchPlan, epoch_index
 from ..eval.export import postprocess_thetas, save_model_as_npz
 
 
 class FederatedClient:
+    _shared_hook = None               # see the ``shared`` property
+
     def __init__(self, client_id: int, tm, dataset, max_iters: int, logger=None, seed: int = 0,
                  save_path: Optional[str] = None, log_every: int = 0, n_samples: int = 20,
                  epoch_snapshots: bool = False, agg: str = "params"):
@@ -88,6 +92,11 @@ class FederatedClient:
         self._pinned = None
         self._events: List = []
         self._slot = 0
+        # the round object's device epoch sums (federation/epoch_sums.py) and this client's
+        # column there; None: the reduction over loss_hist below
+        self._esums = None
+        self._ecol = 0
+        self._epoch_of = epoch_index(self.plan.epoch_end)
         hist = tm.engine.loss_hist
         if hist.device.type == "cuda":
             self._pinned = torch.zeros(64, dtype=torch.float32, pin_memory=True)
@@ -98,6 +107,11 @@ class FederatedClient:
     # ------------------------------------------------------------------ state
     @property
     def shared(self) -> torch.Tensor:
+        """The client's shared state.  A round object that keeps the averaged state elsewhere
+        between replays (rank_round.MultiClientRound's shared read copy) brings this buffer
+        up to date first (``_shared_hook``), so host code may read or write it after any round."""
+        if self._shared_hook is not None:
+            self._shared_hook()
         return self.tm.flat.shared
 
     @property
@@ -188,7 +202,18 @@ class FederatedClient:
         return self.results_saved
 
     # ---- asynchronous epoch summaries
+    def attach_epoch_sums(self, reader, col: int):
+        """``reader`` (federation/epoch_sums.py EpochSums) holds this client's epoch loss sums
+        in column ``col``, kept by the step kernels; None: back to the host path."""
+        self._esums, self._ecol = reader, int(col)
+
     def _queue_epoch_summary(self, first: int, last: int):
+        if self._esums is not None:
+            # the sum is already in its device slot: at most one copy of the slots' row and one
+            # event per epoch-ending round, shared with the rank's other clients
+            dst, ev = self._esums.fetch(last, int(self._epoch_of[last]), self._ecol)
+            self._pending.append((self.current_epoch, self.samples_processed, dst, ev))
+            return
         hist = self.tm.engine.loss_hist
         if hist.device.type != "cuda":
             self._pending.append((self.current_epoch, self.samples_processed,

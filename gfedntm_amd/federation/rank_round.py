@@ -39,6 +39,7 @@ from ..parallel.aggregator import (LOCAL_ALL, LOCAL_BCAST, LOCAL_FIRST, LOCAL_RE
                                    local_fedavg, prepare_local_fedavg)
 from ..utils.misc import graph_capture
 from .client import FederatedClient
+from .epoch_sums import EpochSums
 
 
 def inplace_threshold_bytes() -> int:
@@ -68,6 +69,9 @@ class SingleClientRound:
             logger.info("-- -- FedAvg all-reduce: %s", self.in_step)
         self.method = self.in_step if self.in_step else (None if world == 1 else "rccl")
         self.attach = getattr(client.tm.engine, "fedavg_attach", None) if self.in_step else None
+        # the epoch loss sums kept by the step kernels (federation/epoch_sums.py; None: the
+        # host reduction at epoch ends, which then cut the runs of rounds per replay)
+        self.epoch_sums = EpochSums.attach(self.clients)
 
     @property
     def xgmi(self) -> bool:
@@ -143,6 +147,8 @@ class SingleClientRound:
         return self.client.tm.engine.fedavg_debug() if self.in_step is not None else {}
 
     def close(self):
+        EpochSums.detach(self.clients)
+        self.epoch_sums = None
         if self.in_step is not None and self.client.fused:
             self.client.tm.engine.detach_fedavg()
             self.in_step = None
@@ -206,6 +212,9 @@ class MultiClientRound:
                 c.enable_graph(False)     # the round graph carries every client's step
         if self.fused:
             prepare_local_fedavg(self.shared)
+        # the clients' epoch loss sums, one column each (federation/epoch_sums.py; None: the
+        # host reduction at epoch ends, which then cut the runs of rounds per replay)
+        self.epoch_sums = EpochSums.attach(clients)
         self.fold_plan: Optional[str] = None   # the in-rank FedAvg of the batched round
         self._g = None                    # the one-round graph
         self._gk: Dict[int, object] = {}  # k-round graphs (k > 1)
@@ -223,9 +232,23 @@ class MultiClientRound:
         self._streams = None
         self._side = None
         self._err = None
+        for c in clients:
+            c._shared_hook = self._materialise
         if logger is not None:
             logger.info("-- -- FedAvg: %d local clients folded in-rank, %s across %d ranks",
                         len(clients), self.method or "no collective", world)
+
+    def _materialise(self):
+        """Host code asked for a client's shared state (``FederatedClient.shared``): if the
+        averaged state lives in the shared read copy alone (the last replay was a ``more``
+        one), copy it into every client's buffer behind that replay; the next replay then
+        refreshes the copy from client 0's buffer, so a host write is what the rounds read."""
+        if self._s_live:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("a client's shared state was asked for inside a graph capture")
+            for s in self.shared:
+                s.copy_(self._S)
+            self._s_live = False
 
     def _states_equal(self) -> bool:
         """Every client's shared state is the same (the shared-reads plan has all of them
@@ -550,6 +573,11 @@ class MultiClientRound:
 
     def close(self):
         self._drop_graphs()
+        self._materialise()
+        for c in self.clients:
+            c._shared_hook = None
+        EpochSums.detach(self.clients)
+        self.epoch_sums = None
         for c in self.colls.values():
             if c.xgmi is not None:
                 c.xgmi.close()

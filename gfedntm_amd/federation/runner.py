@@ -48,6 +48,7 @@ from ..utils.misc import graph_capture
 from ..utils.trace import RoundWindow, trace_range
 from .client import FederatedClient
 from .data import ClientCorpus
+from .epoch_sums import EpochSums
 
 
 CTM_TYPES = ("ctm", "zeroshot")
@@ -132,6 +133,53 @@ def federation_coherence(tm, datas, topk: int = 10, matrix: str = "beta", per_to
 def log_coherence(logger, coh: Dict, topk: int):
     logger.info("-- -- Global NPMI@%d: %.4f (TD %.4f, %d documents, %d clients)", topk,
                 float(np.mean(coh["per_topic"])), coh["diversity"], coh["n_docs"], coh["clients"])
+
+
+# ---- runs of rounds per graph replay: where a run ends (pure functions of the plans) ----
+def round_cuts(epoch_ends, heavy, last: int, warmup_end: Optional[int] = None,
+               device_sums: bool = False) -> set:
+    """The rounds after which a run of rounds per graph replay must end whatever the periodic
+    boundaries say: the host-heavy rounds (results / snapshot saves), the last round, the end
+    of a timing warmup -- and, unless the epoch loss sums are kept on the device
+    (federation/epoch_sums.py), every client's epoch ends, where the host then reduces
+    ``loss_hist`` on the round's stream."""
+    ends = {int(r) for r in heavy} | {int(last)}
+    if warmup_end is not None:
+        ends.add(int(warmup_end))
+    if not device_sums:
+        ends.update(int(r) for r in epoch_ends)
+    return ends
+
+
+def host_after_round(r: int, ends, poll_every: int = 0, digest_every: int = 0,
+                     metrics_every: int = 0, checkpoint_every: int = 0) -> bool:
+    """The host needs the state, or the device, after round r: a round of ``ends``
+    (:func:`round_cuts`) or a poll, digest, metrics or checkpoint boundary.  A run ends there
+    and the replay that carries r is not followed by ``more``."""
+    n1 = r + 1
+    return bool(r in ends
+                or (poll_every and n1 % poll_every == 0)
+                or (digest_every and n1 % digest_every == 0)
+                or (metrics_every and n1 % metrics_every == 0)
+                or (checkpoint_every and n1 % checkpoint_every == 0))
+
+
+def run_plan(it: int, kmax: int, ends, **every) -> tuple:
+    """(k, more) of the replay that starts at round ``it``: k rounds, the largest power of two
+    (few graphs are ever captured) within ``kmax`` that does not pass a round the host needs
+    something after; ``more``: the next replay follows with no host access to the state in
+    between.  ``every``: the periodic boundaries of :func:`host_after_round`."""
+    if kmax <= 1:
+        return 1, False
+    r = it
+    while r < it + kmax - 1 and not host_after_round(r, ends, **every):
+        r += 1
+    k = 1 << ((r - it + 1).bit_length() - 1)
+    return k, not host_after_round(it + k - 1, ends, **every)
+
+
+def client_epoch_ends(clients) -> List[int]:
+    return sorted({int(i) for c in clients for i in np.flatnonzero(c.plan.epoch_end)})
 
 
 class LocalFederation:
@@ -230,6 +278,8 @@ class LocalFederation:
             if self.round:
                 self.logger.info("-- -- Resuming the federation at round %d", self.round)
             self.agg.set_reference(self.clients[0].shared)
+        # epoch loss sums kept by the step kernels (None: the host reduction at epoch ends)
+        self.epoch_sums = EpochSums.attach(self.clients)
 
     def _sync(self):
         if self.device.type == "cuda":
@@ -332,17 +382,6 @@ class LocalFederation:
             return 1
         return max(1, int(os.environ.get("GFEDNTM_ROUNDS_PER_GRAPH", "16")))
 
-    def _run_end(self, it: int, kmax: int, ends, timed_end: int) -> int:
-        r = it
-        while r < it + kmax - 1 and r not in ends and r != timed_end:
-            n1 = r + 1
-            if ((self.metrics_every and n1 % self.metrics_every == 0)
-                    or (self.checkpoint_dir and self.checkpoint_every
-                        and n1 % self.checkpoint_every == 0)):
-                break
-            r += 1
-        return r
-
     def _round(self, it: int, k: int = 1):
         """Every client's local step and the FedAvg of round ``it`` (enqueued; k > 1:
         rounds it .. it + k - 1 in one replay of the round graph)."""
@@ -377,19 +416,20 @@ class LocalFederation:
         ends = {self.max_iters - 1}
         if kmax > 1:
             self.prewarm(kmax)
-            for c in self.clients:
-                ends.update(int(i) for i in np.flatnonzero(c.plan.epoch_end))
-                # rounds whose end_round reads the state on the host (round 0's results when
-                # num_epochs <= 0, ...): a run must end there, as run_distributed's do
-                ends.update(int(i) for i in c.host_heavy_rounds())
-        timed_end = start + timing_warmup - 1 if timing_warmup else -1
+            # rounds whose end_round reads the state on the host (round 0's results when
+            # num_epochs <= 0, ...): a run must end there, as run_distributed's do; an epoch
+            # end only while its loss sum is reduced on the host (round_cuts)
+            ends = round_cuts(client_epoch_ends(self.clients),
+                              [r for c in self.clients for r in c.host_heavy_rounds()],
+                              self.max_iters - 1, start + timing_warmup - 1 if timing_warmup else None,
+                              device_sums=self.epoch_sums is not None)
+        every = dict(metrics_every=self.metrics_every,
+                     checkpoint_every=self.checkpoint_every if self.checkpoint_dir else 0)
         covered = start - 1
         with trace_range("rounds"):
             for it in range(self.round, self.max_iters):
                 if it > covered:
-                    k = 1
-                    if kmax > 1:      # (power-of-two runs: few captures, MultiClientRound)
-                        k = 1 << ((self._run_end(it, kmax, ends, timed_end) - it + 1).bit_length() - 1)
+                    k, _ = run_plan(it, kmax, ends, **every)
                     self._round(it, k)
                     covered = it + k - 1
                 done = [c.end_round(it) for c in self.clients]
@@ -790,26 +830,15 @@ def _round_loop(rr, clients, client_ids, cmap, world, rank, device, ctrl, hb, lo
     kmax = getattr(rr, "rounds_per_replay", lambda: 1)()
     if round_hook is not None or corrupt_from is not None or debug_comm:
         kmax = 1
+    # (an epoch end is such a round only while its loss sum is reduced on the host: with
+    # the sums kept by the step kernels -- rr.epoch_sums -- a replay may span it)
     ends = set(align) | {stop_after}
     if kmax > 1:
-        for c in clients:
-            ends.update(int(i) for i in np.flatnonzero(c.plan.epoch_end))
-        if timing_warmup:
-            ends.add(start + timing_warmup - 1)
-
-    def host_after(r: int) -> bool:
-        """The host needs the state, or the device, after round r."""
-        n1 = r + 1
-        return bool(r in ends
-                    or (poll_every and n1 % poll_every == 0) or (digest_every and n1 % digest_every == 0)
-                    or (metrics_every and n1 % metrics_every == 0)
-                    or (checkpoint_dir and checkpoint_every and n1 % checkpoint_every == 0))
-
-    def run_end(it: int) -> int:
-        r = it
-        while r < it + kmax - 1 and not host_after(r):
-            r += 1
-        return r
+        ends = round_cuts(client_epoch_ends(clients), align, stop_after,
+                          start + timing_warmup - 1 if timing_warmup else None,
+                          device_sums=getattr(rr, "epoch_sums", None) is not None)
+    every = dict(poll_every=poll_every, digest_every=digest_every, metrics_every=metrics_every,
+                 checkpoint_every=checkpoint_every if checkpoint_dir else 0)
 
     if kmax > 1 and hasattr(rr, "prewarm"):
         rr.prewarm(kmax)              # every k-round graph captured before the first round
@@ -821,9 +850,8 @@ def _round_loop(rr, clients, client_ids, cmap, world, rank, device, ctrl, hb, lo
             if it > covered:
                 # (a power of two: at most log2(kmax) + 1 graphs are ever captured -- a
                 # capture inside the timed rounds costs milliseconds)
-                k = 1 << ((run_end(it) - it + 1).bit_length() - 1) if kmax > 1 else 1
                 # (more: the next replay follows with no host access to the state in between)
-                more = kmax > 1 and not host_after(it + k - 1)
+                k, more = run_plan(it, kmax, ends, **every)
                 if k > 1:
                     rr.step(it, hb, k, more=more)
                 else:

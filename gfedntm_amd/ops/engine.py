@@ -38,7 +38,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from ..data.bow import BatchPlan, DeviceCSR
+from ..data.bow import BatchPlan, DeviceCSR, epoch_index
 from ..models.engine import EngineBase
 from ..utils.flat import ALIGN, slot_view
 from ..utils.misc import graph_capture
@@ -1048,6 +1048,16 @@ class FusedEngine(EngineBase):
         m.kl_hist = self.kl_hist.data_ptr() if self.terms_on else None
         m.rl_hist = self.rl_hist.data_ptr() if self.terms_on else None
         m.n_steps = plan.n_steps
+        # the running epoch loss sum (csrc/gfk_common.h GfkModel.epoch_loss): the steps' epoch
+        # indices and the running sum live here; the slots are the caller's (bind_epoch_sums)
+        eidx = epoch_index(plan.epoch_end)
+        self.n_epochs = int(eidx[-1]) + 1 if len(eidx) else 0
+        self._epoch_of = eidx
+        self._plan_dev["epoch"] = torch.from_numpy(eidx).to(dev)
+        self.epoch_run = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.epoch_sums = None
+        m.epoch_idx, m.epoch_run = None, None
+        m.epoch_loss, m.epoch_stride = None, 0
         self.d_step.zero_()
         self._host_step = 0
         self._invalidate_graph()
@@ -1061,6 +1071,32 @@ class FusedEngine(EngineBase):
             self._m.kl_hist = self.kl_hist.data_ptr() if self.terms_on else None
             self._m.rl_hist = self.rl_hist.data_ptr() if self.terms_on else None
             self._invalidate_graph()
+
+    def bind_epoch_sums(self, slots: Optional[torch.Tensor], col: int = 0):
+        """``slots``: float32 [>= n_epochs, M] on this device; from now on the thread that
+        writes ``loss_hist[s]`` also keeps the fp32 left fold of the epoch's step losses in
+        ``slots[epoch of s, col]`` (csrc/posterior.hip post_epoch_sum), final once the epoch's
+        last step has run.  None: off (the kernels do what they did without it)."""
+        if self.plan is None:
+            raise RuntimeError("bind_data() first")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("bind_epoch_sums inside a graph capture")
+        m = self._m
+        if slots is None:
+            m.epoch_idx, m.epoch_run, m.epoch_loss, m.epoch_stride = None, None, None, 0
+        else:
+            if (slots.dtype != torch.float32 or slots.device != self.device or slots.dim() != 2
+                    or slots.shape[0] < self.n_epochs or not 0 <= col < slots.shape[1]
+                    or slots.stride(1) != 1):
+                raise ValueError("epoch sums: float32 [n_epochs or more, M] on the engine's "
+                                 "device, unit column stride, 0 <= col < M")
+            m.epoch_idx = self._plan_dev["epoch"].data_ptr()
+            m.epoch_run = self.epoch_run.data_ptr()
+            m.epoch_loss = slots.data_ptr() + 4 * int(col)
+            m.epoch_stride = int(slots.stride(0))
+            self.epoch_run.zero_()
+        self.epoch_sums = None if slots is None else slots[:, col]
+        self._invalidate_graph()
 
     def phases(self) -> List[int]:
         if self._m.kind == abi.KIND_LDA:
@@ -1611,12 +1647,32 @@ class FusedEngine(EngineBase):
             raise RuntimeError("external capture is for in-process federations (no collective)")
         self._launch(self.phases())
 
+    def _seed_epoch_run(self, s: int):
+        """A jump to step s: the running epoch sum becomes what the steps of s's epoch before
+        s left in ``loss_hist`` -- their fp32 left fold, the kernels' own order -- so the epoch a
+        resume lands in reports all its steps, bit for bit what an uninterrupted run reports
+        (utils/checkpoint.py restores ``loss_hist``).  0 at an epoch start.  One host read of a
+        few floats where the slots are bound: a jump is rare and never inside a timed loop."""
+        self.epoch_run.zero_()
+        if self.epoch_sums is None or not 0 < s < len(self._epoch_of):
+            return
+        first = s
+        while first > 0 and self._epoch_of[first - 1] == self._epoch_of[s]:
+            first -= 1
+        if first < s:
+            hist = self.loss_hist[first:s].cpu().numpy()
+            acc = np.float32(hist[0])
+            for v in hist[1:]:
+                acc = np.float32(acc + v)
+            self.epoch_run.fill_(float(acc))
+
     def advance_host_step(self, s: int):
         self._host_step = s + 1
 
     def sync_step_counter(self, s: int):
         if s != self._host_step:
             self.d_step.fill_(s)
+            self._seed_epoch_run(s)
             self._host_step = s
             self._launch([abi.PH_BATCH_PREP])   # the step's batch is prepared by the previous one
 

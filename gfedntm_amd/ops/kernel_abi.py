@@ -126,9 +126,10 @@ class GfkModel(C.Structure):
         ("ws_lab", P), ("ws_dlab", P), ("ws_ce", P), ("ws_thd", P),
         ("lab_in_enc", C.c_int32), ("bwd_pre", C.c_int32), ("ws_dt", P),
         ("dev", P), ("dev_upd", P), ("n_batch", C.c_int32), ("ldb", C.c_int32),
-        ("ctx_bgrid", C.c_int32), ("ws_colstat", P),
+        ("ctx_bgrid", C.c_int32), ("epoch_stride", C.c_int32), ("ws_colstat", P),
         ("kl_hist", P), ("rl_hist", P),
         ("off_own", C.c_int64),
+        ("epoch_idx", P), ("epoch_run", P), ("epoch_loss", P),
     ]
 
 

@@ -140,6 +140,11 @@ class FlatState:
 
     @property
     def shared(self) -> torch.Tensor:
+        # The raw view.  While a MultiClientRound runs its shared-reads plan the averaged state
+        # may live in the round's shared copy alone between replays (a ``more`` chain, which
+        # epoch ends no longer break): host code in a round loop reads and writes the state
+        # through ``FederatedClient.shared``, which brings this buffer up to date first, or at a
+        # round declared in ``host_heavy_rounds()``
         return self.buffer[: self.n_shared]
 
     def param_slots(self) -> List[Slot]:
