@@ -240,6 +240,10 @@ constexpr int GFK_POST_ROWS4 = 4194304;
 // 8-wave workgroups, three per CU, so all clients' tiles are resident at once
 // (csrc/prodlda.hip prodlda_bwd8_kernel: bmax 64, K <= 64, fp32)
 constexpr int GFK_BWD_BATCH8 = 8388608;
+// stage_flags bit 24 (GFK_WIN_WAVES6, batched launches, with bit 9): win_update's 8-wave dense
+// tiles compiled for 6 waves per SIMD (80 VGPRs, three workgroups per CU: no spills) where
+// all clients' tiles and jobs are resident at once (csrc/update.hip gfk_win_update_k)
+constexpr int GFK_WIN_WAVES6 = 16777216;
 // rows whose own-row vectors post_bwd keeps in LDS at once (1: the serial shapes)
 __host__ __device__ __forceinline__ int gfk_post_joint_rows(int stage_flags) {
   return !(stage_flags & GFK_POST_JOINT) ? 1 : (stage_flags & GFK_POST_ROWS4) ? 4 : 2;
@@ -405,6 +409,15 @@ namespace gfk {
       (m).dbg[slot] = __builtin_amdgcn_s_memtime();                               \
     __builtin_amdgcn_sched_barrier(0);                                            \
   } while (0)
+// ... thread 0 of every workgroup where `cond` holds (one it names, where workgroup 0 has
+// another role), in s_memtime cycles
+#define GFK_STAMP_WG(m, cond, slot)                                               \
+  do {                                                                            \
+    __builtin_amdgcn_sched_barrier(0);                                            \
+    if ((cond) && threadIdx.x == 0 && (m).dbg)                                    \
+      (m).dbg[slot] = __builtin_amdgcn_s_memtime();                               \
+    __builtin_amdgcn_sched_barrier(0);                                            \
+  } while (0)
 // ... thread 0 of every workgroup where `cond` holds (a batched launch: the clients whose
 // descriptor carries dbg), in s_memrealtime ticks (100 MHz, one counter for the whole chip:
 // s_memtime of two CUs cannot be compared)
@@ -415,9 +428,21 @@ namespace gfk {
       (m).dbg[slot] = __builtin_amdgcn_s_memrealtime();                           \
     __builtin_amdgcn_sched_barrier(0);                                            \
   } while (0)
+// ... the same once the wave's outstanding global loads and stores have completed
+#define GFK_STAMP_IF_VM(m, cond, slot)                                            \
+  do {                                                                            \
+    __builtin_amdgcn_sched_barrier(0);                                            \
+    if ((cond) && threadIdx.x == 0 && (m).dbg) {                                  \
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                            \
+      (m).dbg[slot] = __builtin_amdgcn_s_memrealtime();                           \
+    }                                                                             \
+    __builtin_amdgcn_sched_barrier(0);                                            \
+  } while (0)
 #else
 #define GFK_STAMP(m, slot) do { } while (0)
+#define GFK_STAMP_WG(m, cond, slot) do { } while (0)
 #define GFK_STAMP_IF(m, cond, slot) do { } while (0)
+#define GFK_STAMP_IF_VM(m, cond, slot) do { } while (0)
 #endif
 
 // Philox4x32-10 counter-based RNG: stateless, so every kernel (and every graph

@@ -23,6 +23,8 @@
 // Deterministic, no atomics, W_in's gradient is never materialised in fused mode.
 // One extra workgroup prepares the next minibatch (gfk_common.h).
 #define GFK_BATCHED_COPY 1   // batched kernels copy their descriptor (gfk_common.h gfk_model)
+#include <type_traits>
+
 #include "gfk_common.h"
 #include "gfk_launch.h"
 
@@ -598,8 +600,14 @@ __device__ __forceinline__ void win_tile_ctx(const GfkModel& m, float* smem, int
 // dynamic LDS: max(W_in tile: xt[64][stride_a(B)] + dz[B][stride_b(H0P)], weight job: 2 B 80)
 // (8-wave shape: at most 64 VGPRs, so the 4 workgroups its 37 KB of LDS allows per CU also
 // fit the register file -- the batched instance compiled to 68 VGPRs, 7 waves per SIMD)
-template <int UT, bool GB = false>
-__global__ void __launch_bounds__(UT, UT == 512 ? 8 : 1) gfk_win_update_k(GfkArgT<GB> ga, GfkUArgT<GB> gua) {
+// WPS: the waves per SIMD it is compiled for.  The 8-wave shape at 8 spills (the job paths
+// alone need ~86 VGPRs); at 6 (80 VGPRs, three workgroups per CU) it does not -- the
+// batched instance of stage_flags GFK_WIN_WAVES6, for launches whose workgroups three per
+// CU hold at once.  That instance has a tile body of its own (the second one below), which
+// stages the tile in one global round and needs the registers: at 64 VGPRs the same body
+// spilled 11 and measured slower than the first one (profiles/r13/)
+template <int UT, bool GB = false, int WPS = (UT == 512 ? 8 : 1)>
+__global__ void __launch_bounds__(UT, WPS) gfk_win_update_k(GfkArgT<GB> ga, GfkUArgT<GB> gua) {
   const GfkModel& m = gfk_model(ga);
   const GfkUpdate& U = gfk_upd(gua);
   constexpr int UW = UT / 64;
@@ -607,144 +615,137 @@ __global__ void __launch_bounds__(UT, UT == 512 ? 8 : 1) gfk_win_update_k(GfkArg
   const int nt_here = m.n_tiles;
   {
     const int r = (int)gfk_bx() - nt_here;
-    if (r >= 0 && r < U.n_w) { weight_job<UT, GB>(m, U.w[r], smem); return; }
-    if (r >= U.n_w && r < U.n_w + U.n_v) { vector_job<UT, false, GB>(m, U.v[r - U.n_w]); return; }
-    if (r == U.n_w + U.n_v) { prepare_next_batch(m, reinterpret_cast<int*>(smem)); return; }
+    // (stamps of a batched launch, tools/stamps.py --clients: the first weight job, the last
+    // vector job and the next-batch workgroup, slots 656 / 658 / 660 + entry, end)
+    if (r >= 0 && r < U.n_w) {
+      GFK_STAMP_IF(m, m.n_batch > 1 && r == 0, 656);
+      weight_job<UT, GB>(m, U.w[r], smem);
+      GFK_STAMP_IF_VM(m, m.n_batch > 1 && r == 0, 657);
+      return;
+    }
+    if (r >= U.n_w && r < U.n_w + U.n_v) {
+      GFK_STAMP_IF(m, m.n_batch > 1 && r == U.n_w + U.n_v - 1, 658);
+      vector_job<UT, false, GB>(m, U.v[r - U.n_w]);
+      GFK_STAMP_IF_VM(m, m.n_batch > 1 && r == U.n_w + U.n_v - 1, 659);
+      return;
+    }
+    if (r == U.n_w + U.n_v) {
+      GFK_STAMP_IF(m, m.n_batch > 1, 660);
+      prepare_next_batch(m, reinterpret_cast<int*>(smem));
+      GFK_STAMP_IF_VM(m, m.n_batch > 1, 661);
+      return;
+    }
   }
-  const bool zs = m.ctx_fused == 2;            // ZeroShotTM: W_in is the dense [C, H0] layer
-  if (m.input == GFK_IN_CONTEXTUAL && !zs) return;   // (host GEMMs when not fused)
-  const int rr = (int)gfk_bx() - (nt_here + U.n_w + U.n_v + 1);
-  const bool ctxt = rr >= 0;                   // a Wc tile (CombinedTM) / W tile (ZeroShotTM)
-  if (zs && !ctxt) return;                     // ZeroShotTM has no bag-of-words half
-  const int tid = threadIdx.x, lane = tid & 63, wave = uniform(tid >> 6);
-  int B = m.bmax, H0 = m.H[0], V = zs ? m.C : m.V, n_tiles = m.n_tiles;
-  const int32_t *tstart = m.ws_tstart, *indices = m.indices, *nbp = m.ws_nb;
-  const float *values = m.values, *dz0 = m.ws_dz[0];
-  float* w_in = m.w_in + (ctxt && !zs ? (size_t)m.V * m.H[0] : 0);
-  keep(B, H0, V, n_tiles, tstart, indices, nbp, values, dz0, w_in);
-  const int H0P = rup(H0, 16);
-  const int XS = stride_a(B), ZS = stride_b(H0P);
-  float* xt = smem;
-  float* dz = smem + 64 * XS;
-  const int tile = ctxt ? rr : (int)gfk_bx(), c0 = tile * 64;
+  if constexpr (WPS != 6) {
+  // ---- the tile body of the shapes' own instances ----
+    const bool zs = m.ctx_fused == 2;            // ZeroShotTM: W_in is the dense [C, H0] layer
+    if (m.input == GFK_IN_CONTEXTUAL && !zs) return;   // (host GEMMs when not fused)
+    const int rr = (int)gfk_bx() - (nt_here + U.n_w + U.n_v + 1);
+    const bool ctxt = rr >= 0;                   // a Wc tile (CombinedTM) / W tile (ZeroShotTM)
+    if (zs && !ctxt) return;                     // ZeroShotTM has no bag-of-words half
+    const int tid = threadIdx.x, lane = tid & 63, wave = uniform(tid >> 6);
+    int B = m.bmax, H0 = m.H[0], V = zs ? m.C : m.V, n_tiles = m.n_tiles;
+    const int32_t *tstart = m.ws_tstart, *indices = m.indices, *nbp = m.ws_nb;
+    const float *values = m.values, *dz0 = m.ws_dz[0];
+    float* w_in = m.w_in + (ctxt && !zs ? (size_t)m.V * m.H[0] : 0);
+    keep(B, H0, V, n_tiles, tstart, indices, nbp, values, dz0, w_in);
+    const int H0P = rup(H0, 16);
+    const int XS = stride_a(B), ZS = stride_b(H0P);
+    float* xt = smem;
+    float* dz = smem + 64 * XS;
+    const int tile = ctxt ? rr : (int)gfk_bx(), c0 = tile * 64;
 
-  GFK_STAMP(m, 40);
-  // ---- staging: dz0 rows (zero padding), zero x^T tile, the tile's CSR extents ----
-  const int nb = *nbp;
-  if (H0P <= 64) {            // column tid % 64, rows tid / 64 + UT / 64 j: no runtime division
-    const int c = tid & 63;
-    if (c < H0P)
-      for (int r = tid >> 6; r < B; r += UT / 64)
+    GFK_STAMP(m, 40);
+#ifdef GFK_STAMPS
+    const bool stamp2 = m.n_batch > 1 && !ctxt && (tile == 0 || tile == n_tiles - 1);
+    const int slot2 = tile == 0 ? 640 : 648;
+#endif
+    GFK_STAMP_IF(m, stamp2, slot2);
+    // ---- staging: dz0 rows (zero padding), zero x^T tile, the tile's CSR extents ----
+    const int nb = *nbp;
+    if (H0P <= 64) {            // column tid % 64, rows tid / 64 + UT / 64 j: no runtime division
+      const int c = tid & 63;
+      if (c < H0P)
+        for (int r = tid >> 6; r < B; r += UT / 64)
+          dz[r * ZS + c] = (c < H0 && r < nb) ? dz0[r * H0 + c] : 0.f;
+    } else {
+      for (int i = tid; i < B * H0P; i += UT) {
+        const int r = i / H0P, c = i % H0P;
         dz[r * ZS + c] = (c < H0 && r < nb) ? dz0[r * H0 + c] : 0.f;
-  } else {
-    for (int i = tid; i < B * H0P; i += UT) {
-      const int r = i / H0P, c = i % H0P;
-      dz[r * ZS + c] = (c < H0 && r < nb) ? dz0[r * H0 + c] : 0.f;
-    }
-  }
-  if (zs) {                   // x_ctx^T tile: the batch rows' contextual features
-    for (int i = tid; i < B * 64; i += UT) {
-      const int b = i >> 6, v = i & 63;
-      xt[v * XS + b] = (b < nb && c0 + v < V) ? m.ctx[(size_t)m.ws_doc[b] * V + c0 + v] : 0.f;
-    }
-  } else if (ctxt) {          // A^T tile: the adapted rows (slab 0 of ctx_fwd's output)
-    const float* ag = m.ws_actx + (size_t)tile * B * 64;
-    for (int i = tid; i < B * 64; i += UT) {
-      const int b = i >> 6, v = i & 63;
-      xt[v * XS + b] = b < nb ? ag[i] : 0.f;
-    }
-  } else {
-    for (int i = tid; i < 64 * XS; i += UT) xt[i] = 0.f;
-  }
-  // 16 threads per row: the row's non-zeros inside this tile (rows tid/16 + 32 i,
-  // i < B / 32 -- the tile-start loads of every row are issued in the staging round)
-  constexpr int XR = 128 / (UT / 16);          // row slots per thread (bmax <= 128)
-  const int row = tid >> 4, sub = tid & 15;
-  int xe0[XR], xe1[XR];
-#pragma unroll
-  for (int i = 0; i < XR; ++i) {
-    const int r = row + i * (UT / 16);
-    xe0[i] = xe1[i] = 0;
-    if (!ctxt && r < nb && r < B) {
-      const int32_t* ts = tstart + (size_t)r * (n_tiles + 1) + tile;
-      xe0[i] = ts[0];
-      xe1[i] = ts[1];
-    }
-  }
-  // prefetch the optimizer state of this lane's outputs: subtiles t = wave + UW u
-  // (16x16 each; H0 <= 64 -> at most 16 subtiles, one pass; wider layers take passes
-  // of UW * PU subtiles below, the later ones prefetched after the scatter)
-  const int MT = 4, NT = H0P / 16;
-  constexpr int PU = 16 / UW;
-  float pp[PU][4], pm[PU][4], pv[PU][4];
-  const bool fused = m.update_mode == 1;
-  // FLAT (H0 <= 64, one pass): a tile's W_in block [64, H0] is contiguous, so the
-  // epilogue moves p / m / v as flat quads (float4 when 16-B aligned): every load /
-  // store instruction covers whole cache lines, instead of the MFMA output layout's
-  // 4 rows x 64 B.  The gradient tile goes through LDS (the x^T buffer, free after the
-  // MFMAs).  Quad q of the block is thread (q % UT)'s slot q / UT.
-  // (the 8-wave large-vocabulary shape only: with one round of 16-wave workgroups the
-  // extra LDS pass and barriers measured slower than the bytes they save)
-  const bool flat = UT == 512 && NT <= 4;
-  const int nel = (min(V, c0 + 64) - c0) * H0;          // the block's elements
-  float* wblk = w_in + (size_t)c0 * H0;
-  const bool al4 = ((uintptr_t)wblk % 16 == 0) && m.off_m % 4 == 0 && m.off_v % 4 == 0 &&
-                   m.off_g % 4 == 0;
-  auto ld4 = [&](const float* q, int e) {      // elements e..e+3 of the block (bounded)
-    if (al4 && e + 3 < nel) return *reinterpret_cast<const f32x4*>(q + e);
-    f32x4 r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) r[i] = e + i < nel ? q[e + i] : 0.f;
-    return r;
-  };
-  constexpr int FQ = 64 * 64 / 4 / UT;         // quads per thread (H0 <= 64)
-  static_assert(FQ <= PU, "flat epilogue reuses the prefetch registers");
-  if (flat) {
-#pragma unroll
-    for (int u = 0; u < FQ; ++u) {
-      const int e = 4 * (tid + UT * u);
-      f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = a, c = a;
-      if (fused && e < nel) { a = ld4(wblk, e); b = ld4(wblk + m.off_m, e); c = ld4(wblk + m.off_v, e); }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { pp[u][i] = a[i]; pm[u][i] = b[i]; pv[u][i] = c[i]; }
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < PU; ++u) {
-    if (flat) break;
-    const int t = wave + UW * u;
-    const int i0 = (t / NT) * 16, j0 = (t % NT) * 16;
-    const int j = min(j0 + (lane & 15), H0 - 1);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int v = min(c0 + i0 + (lane >> 4) * 4 + r, V - 1);
-      float* p = w_in + (size_t)v * H0 + j;
-      pp[u][r] = pm[u][r] = pv[u][r] = 0.f;
-      if (t < MT * NT && fused) {
-        pp[u][r] = *p;
-        pm[u][r] = p[m.off_m];
-        pv[u][r] = p[m.off_v];
       }
     }
-  }
-  __syncthreads();
+    if (zs) {                   // x_ctx^T tile: the batch rows' contextual features
+      for (int i = tid; i < B * 64; i += UT) {
+        const int b = i >> 6, v = i & 63;
+        xt[v * XS + b] = (b < nb && c0 + v < V) ? m.ctx[(size_t)m.ws_doc[b] * V + c0 + v] : 0.f;
+      }
+    } else if (ctxt) {          // A^T tile: the adapted rows (slab 0 of ctx_fwd's output)
+      const float* ag = m.ws_actx + (size_t)tile * B * 64;
+      for (int i = tid; i < B * 64; i += UT) {
+        const int b = i >> 6, v = i & 63;
+        xt[v * XS + b] = b < nb ? ag[i] : 0.f;
+      }
+    } else {
+      for (int i = tid; i < 64 * XS; i += UT) xt[i] = 0.f;
+    }
+    // 16 threads per row: the row's non-zeros inside this tile (rows tid/16 + 32 i,
+    // i < B / 32 -- the tile-start loads of every row are issued in the staging round)
+    constexpr int XR = 128 / (UT / 16);          // row slots per thread (bmax <= 128)
+    const int row = tid >> 4, sub = tid & 15;
+    int xe0[XR], xe1[XR];
 #pragma unroll
-  for (int i = 0; i < XR; ++i) {
-    const int r = row + i * (UT / 16);
-    for (int e = xe0[i] + sub; e < xe1[i]; e += 16) xt[(indices[e] - c0) * XS + r] = values[e];
-  }
-  __syncthreads();
-
-  GFK_STAMP(m, 41);
-  // ---- G[v, j] = sum_b xt[v, b] dz[b, j] and the update ----
-  const AdamCoef ac = adam_coef(m);
-  const bool sh = is_shared(m, w_in);
-  f32x4 gk[PU];
-  for (int pass = 0; pass * UW * PU < MT * NT; ++pass) {
-  if (pass > 0) {             // wide input layers (H0 > 64): the next subtiles' state
+    for (int i = 0; i < XR; ++i) {
+      const int r = row + i * (UT / 16);
+      xe0[i] = xe1[i] = 0;
+      if (!ctxt && r < nb && r < B) {
+        const int32_t* ts = tstart + (size_t)r * (n_tiles + 1) + tile;
+        xe0[i] = ts[0];
+        xe1[i] = ts[1];
+      }
+    }
+    GFK_STAMP_IF_VM(m, stamp2, slot2 + 1);
+    // prefetch the optimizer state of this lane's outputs: subtiles t = wave + UW u
+    // (16x16 each; H0 <= 64 -> at most 16 subtiles, one pass; wider layers take passes
+    // of UW * PU subtiles below, the later ones prefetched after the scatter)
+    const int MT = 4, NT = H0P / 16;
+    constexpr int PU = 16 / UW;
+    float pp[PU][4], pm[PU][4], pv[PU][4];
+    const bool fused = m.update_mode == 1;
+    // FLAT (H0 <= 64, one pass): a tile's W_in block [64, H0] is contiguous, so the
+    // epilogue moves p / m / v as flat quads (float4 when 16-B aligned): every load /
+    // store instruction covers whole cache lines, instead of the MFMA output layout's
+    // 4 rows x 64 B.  The gradient tile goes through LDS (the x^T buffer, free after the
+    // MFMAs).  Quad q of the block is thread (q % UT)'s slot q / UT.
+    // (the 8-wave large-vocabulary shape only: with one round of 16-wave workgroups the
+    // extra LDS pass and barriers measured slower than the bytes they save)
+    const bool flat = UT == 512 && NT <= 4;
+    const int nel = (min(V, c0 + 64) - c0) * H0;          // the block's elements
+    float* wblk = w_in + (size_t)c0 * H0;
+    const bool al4 = ((uintptr_t)wblk % 16 == 0) && m.off_m % 4 == 0 && m.off_v % 4 == 0 &&
+                     m.off_g % 4 == 0;
+    auto ld4 = [&](const float* q, int e) {      // elements e..e+3 of the block (bounded)
+      if (al4 && e + 3 < nel) return *reinterpret_cast<const f32x4*>(q + e);
+      f32x4 r;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) r[i] = e + i < nel ? q[e + i] : 0.f;
+      return r;
+    };
+    constexpr int FQ = 64 * 64 / 4 / UT;         // quads per thread (H0 <= 64)
+    static_assert(FQ <= PU, "flat epilogue reuses the prefetch registers");
+    if (flat) {
+#pragma unroll
+      for (int u = 0; u < FQ; ++u) {
+        const int e = 4 * (tid + UT * u);
+        f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = a, c = a;
+        if (fused && e < nel) { a = ld4(wblk, e); b = ld4(wblk + m.off_m, e); c = ld4(wblk + m.off_v, e); }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { pp[u][i] = a[i]; pm[u][i] = b[i]; pv[u][i] = c[i]; }
+      }
+    }
 #pragma unroll
     for (int u = 0; u < PU; ++u) {
-      const int t = pass * UW * PU + wave + UW * u;
+      if (flat) break;
+      const int t = wave + UW * u;
       const int i0 = (t / NT) * 16, j0 = (t % NT) * 16;
       const int j = min(j0 + (lane & 15), H0 - 1);
 #pragma unroll
@@ -759,85 +760,449 @@ __global__ void __launch_bounds__(UT, UT == 512 ? 8 : 1) gfk_win_update_k(GfkArg
         }
       }
     }
-  }
+    __syncthreads();
+    GFK_STAMP_IF(m, stamp2, slot2 + 2);
 #pragma unroll
-  for (int u = 0; u < PU; ++u) {
-    const int t = pass * UW * PU + wave + UW * u;
-    if (t >= MT * NT) break;
-    const int i0 = (t / NT) * 16, j0 = (t % NT) * 16;
-    const float* ap = xt + (i0 + (lane & 15)) * XS + (lane >> 4);
-    const float* bp = dz + (lane >> 4) * ZS + j0 + (lane & 15);
-    f32x4 c0v = {0.f, 0.f, 0.f, 0.f}, c1v = {0.f, 0.f, 0.f, 0.f};
-    for (int k = 0; k < B; k += 8) {
-      c0v = mfma16x16x4(ap[k], bp[k * ZS], c0v);
-      c1v = mfma16x16x4(ap[k + 4], bp[(k + 4) * ZS], c1v);
+    for (int i = 0; i < XR; ++i) {
+      const int r = row + i * (UT / 16);
+      for (int e = xe0[i] + sub; e < xe1[i]; e += 16) xt[(indices[e] - c0) * XS + r] = values[e];
     }
-    const f32x4 g = c0v + c1v;
-    const int j = j0 + (lane & 15);
-    if (flat) {               // park the gradient in registers until every wave is done
-      gk[u] = g;
-      continue;
-    }
+    __syncthreads();
+
+    GFK_STAMP(m, 41);
+    GFK_STAMP_IF(m, stamp2, slot2 + 3);
+    // ---- G[v, j] = sum_b xt[v, b] dz[b, j] and the update ----
+    const AdamCoef ac = adam_coef(m);
+    const bool sh = is_shared(m, w_in);
+    f32x4 gk[PU];
+    for (int pass = 0; pass * UW * PU < MT * NT; ++pass) {
+    if (pass > 0) {             // wide input layers (H0 > 64): the next subtiles' state
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int v = c0 + i0 + (lane >> 4) * 4 + r;
-      if (v >= V || j >= H0) continue;
-      float* p = w_in + (size_t)v * H0 + j;
-      if (!fused) {
-        p[m.off_g] = g[r];
-      } else {
-        float mo = pm[u][r], vo = pv[u][r];
-        float np = adam_update(pp[u][r], g[r], mo, vo, ac);
-        if (sh && m.fed_scale_on) np *= m.fed_scale;
-        p[m.off_m] = mo;
-        p[m.off_v] = vo;
-        p[gfk_own<GB>(m)] = np;
+      for (int u = 0; u < PU; ++u) {
+        const int t = pass * UW * PU + wave + UW * u;
+        const int i0 = (t / NT) * 16, j0 = (t % NT) * 16;
+        const int j = min(j0 + (lane & 15), H0 - 1);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int v = min(c0 + i0 + (lane >> 4) * 4 + r, V - 1);
+          float* p = w_in + (size_t)v * H0 + j;
+          pp[u][r] = pm[u][r] = pv[u][r] = 0.f;
+          if (t < MT * NT && fused) {
+            pp[u][r] = *p;
+            pm[u][r] = p[m.off_m];
+            pv[u][r] = p[m.off_v];
+          }
+        }
       }
     }
-  }
-  }
-  if (flat) {
-    // the gradient tile [64, H0] into x^T's buffer in the block's own (flat) order
-    __syncthreads();
 #pragma unroll
     for (int u = 0; u < PU; ++u) {
-      const int t = wave + UW * u;
+      const int t = pass * UW * PU + wave + UW * u;
       if (t >= MT * NT) break;
-      const int i0 = (t / NT) * 16, j0 = (t % NT) * 16, j = j0 + (lane & 15);
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (j < H0) xt[(i0 + (lane >> 4) * 4 + r) * H0 + j] = gk[u][r];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < FQ; ++u) {
-      const int e = 4 * (tid + UT * u);
-      if (e >= nel) break;
-      const f32x4 g = *reinterpret_cast<const f32x4*>(xt + e);
-      f32x4 np, mo, vo;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float a = pm[u][i], b = pv[u][i];
-        float x = fused ? adam_update(pp[u][i], g[i], a, b, ac) : g[i];
-        np[i] = sh && m.fed_scale_on && fused ? x * m.fed_scale : x;
-        mo[i] = a;
-        vo[i] = b;
+      const int i0 = (t / NT) * 16, j0 = (t % NT) * 16;
+      const float* ap = xt + (i0 + (lane & 15)) * XS + (lane >> 4);
+      const float* bp = dz + (lane >> 4) * ZS + j0 + (lane & 15);
+      f32x4 c0v = {0.f, 0.f, 0.f, 0.f}, c1v = {0.f, 0.f, 0.f, 0.f};
+      for (int k = 0; k < B; k += 8) {
+        c0v = mfma16x16x4(ap[k], bp[k * ZS], c0v);
+        c1v = mfma16x16x4(ap[k + 4], bp[(k + 4) * ZS], c1v);
       }
-      auto st4 = [&](float* q, const f32x4& x) {
-        if (al4 && e + 3 < nel) { *reinterpret_cast<f32x4*>(q + e) = x; return; }
+      const f32x4 g = c0v + c1v;
+      const int j = j0 + (lane & 15);
+      if (flat) {               // park the gradient in registers until every wave is done
+        gk[u] = g;
+        continue;
+      }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) if (e + i < nel) q[e + i] = x[i];
-      };
-      if (!fused) {
-        st4(wblk + m.off_g, np);
-      } else {
-        st4(wblk + m.off_m, mo);
-        st4(wblk + m.off_v, vo);
-        st4(wblk + gfk_own<GB>(m), np);
+      for (int r = 0; r < 4; ++r) {
+        const int v = c0 + i0 + (lane >> 4) * 4 + r;
+        if (v >= V || j >= H0) continue;
+        float* p = w_in + (size_t)v * H0 + j;
+        if (!fused) {
+          p[m.off_g] = g[r];
+        } else {
+          float mo = pm[u][r], vo = pv[u][r];
+          float np = adam_update(pp[u][r], g[r], mo, vo, ac);
+          if (sh && m.fed_scale_on) np *= m.fed_scale;
+          p[m.off_m] = mo;
+          p[m.off_v] = vo;
+          p[gfk_own<GB>(m)] = np;
+        }
       }
     }
+    }
+    if (flat) {
+      // the gradient tile [64, H0] into x^T's buffer in the block's own (flat) order
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < PU; ++u) {
+        const int t = wave + UW * u;
+        if (t >= MT * NT) break;
+        const int i0 = (t / NT) * 16, j0 = (t % NT) * 16, j = j0 + (lane & 15);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (j < H0) xt[(i0 + (lane >> 4) * 4 + r) * H0 + j] = gk[u][r];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < FQ; ++u) {
+        const int e = 4 * (tid + UT * u);
+        if (e >= nel) break;
+        const f32x4 g = *reinterpret_cast<const f32x4*>(xt + e);
+        f32x4 np, mo, vo;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          float a = pm[u][i], b = pv[u][i];
+          float x = fused ? adam_update(pp[u][i], g[i], a, b, ac) : g[i];
+          np[i] = sh && m.fed_scale_on && fused ? x * m.fed_scale : x;
+          mo[i] = a;
+          vo[i] = b;
+        }
+        auto st4 = [&](float* q, const f32x4& x) {
+          if (al4 && e + 3 < nel) { *reinterpret_cast<f32x4*>(q + e) = x; return; }
+#pragma unroll
+          for (int i = 0; i < 4; ++i) if (e + i < nel) q[e + i] = x[i];
+        };
+        if (!fused) {
+          st4(wblk + m.off_g, np);
+        } else {
+          st4(wblk + m.off_m, mo);
+          st4(wblk + m.off_v, vo);
+          st4(wblk + gfk_own<GB>(m), np);
+        }
+      }
+    }
+    GFK_STAMP(m, 42);
+    GFK_STAMP_IF_VM(m, stamp2, slot2 + 4);
+  } else {
+  // ---- the 6-waves-per-SIMD instance: the staging as ONE global round (it holds the round's
+  //      loads in registers the 64-VGPR instances do not have: there it measured slower) ----
+    const bool zs = m.ctx_fused == 2;            // ZeroShotTM: W_in is the dense [C, H0] layer
+    if (m.input == GFK_IN_CONTEXTUAL && !zs) return;   // (host GEMMs when not fused)
+    const int rr = (int)gfk_bx() - (nt_here + U.n_w + U.n_v + 1);
+    const bool ctxt = rr >= 0;                   // a Wc tile (CombinedTM) / W tile (ZeroShotTM)
+    if (zs && !ctxt) return;                     // ZeroShotTM has no bag-of-words half
+    const int tid = threadIdx.x, lane = tid & 63, wave = uniform(tid >> 6);
+    int B = m.bmax, H0 = m.H[0], V = zs ? m.C : m.V, n_tiles = m.n_tiles;
+    // (global address space: the batched descriptor's pointers are generic, and one pending
+    // FLAT load turns every later wait into vmcnt(0) lgkmcnt(0) -- no load could stay in flight)
+    typedef const __attribute__((address_space(1))) int32_t* gci_t;
+    typedef const __attribute__((address_space(1))) float* gcf_t;
+    typedef __attribute__((address_space(1))) float* gf_t;
+    typedef __attribute__((address_space(1))) f32x4* gq_t;
+    // element at a 32-bit BYTE offset from a uniform base: the offset stays one VGPR (the scalar
+    // base + 32-bit offset form of the load), not a 64-bit address pair per load in flight
+    auto at32 = [](auto base, unsigned byte_off) {
+      typedef __attribute__((address_space(1))) char* gch_t;
+      return *(decltype(base))((gch_t)base + byte_off);
+    };
+    gci_t tstart = (gci_t)m.ws_tstart, indices = (gci_t)m.indices, nbp = (gci_t)m.ws_nb;
+    gcf_t values = (gcf_t)m.values, dz0 = (gcf_t)m.ws_dz[0];
+    const float* w_in_flat = m.w_in + (ctxt && !zs ? (size_t)m.V * m.H[0] : 0);
+    gf_t w_in = (gf_t)w_in_flat;
+    keep(B, H0, V, n_tiles, tstart, indices, nbp, values, dz0, w_in);
+    const int H0P = rup(H0, 16);
+    const int XS = stride_a(B), ZS = stride_b(H0P);
+    float* xt = smem;
+    float* dz = smem + 64 * XS;
+    const int tile = ctxt ? rr : (int)gfk_bx(), c0 = tile * 64;
+    const int MT = 4, NT = H0P / 16;
+    const bool fused = m.update_mode == 1;
+    const int nel = (min(V, c0 + 64) - c0) * H0;          // the block's elements
+    gf_t wblk = w_in + (size_t)c0 * H0;
+    const bool al4 = ((uintptr_t)wblk % 16 == 0) && m.off_m % 4 == 0 && m.off_v % 4 == 0 &&
+                     m.off_g % 4 == 0;
+    // FLAT (H0 <= 64, one pass): a tile's W_in block [64, H0] is contiguous, so the
+    // epilogue moves p / m / v as flat quads (whole float4: 16-B aligned blocks of a multiple
+    // of 4 elements; other blocks take the subtile layout): every load / store instruction
+    // covers whole cache lines, instead of the MFMA output layout's 4 rows x 64 B.  The
+    // gradient tile goes through LDS (the x^T buffer, free after the MFMAs).  Quad q of the
+    // block is thread (q % UT)'s slot q / UT.
+    // (the 8-wave large-vocabulary shape only: with one round of 16-wave workgroups the
+    // extra LDS pass and barriers measured slower than the bytes they save)
+    // The tile body is compiled once per layout (a compile-time `flat`): the flat prefetch is
+    // then straight-line code, and a load issued in it can stay in flight -- behind a
+    // run-time branch the compiler's wait-count pass merges the paths and waits for everything.
+    const bool flat_rt = uniform(UT == 512 && NT <= 4 && al4 && nel % 4 == 0 && nel >= 4) != 0;
+
+    GFK_STAMP_WG(m, !ctxt && tile == 0, 40);
+    // batched launches: the first-tile and the last-tile workgroup, slots 640 / 648 + entry,
+    // tile extents landed, first barrier passed, scatter done, end
+#ifdef GFK_STAMPS
+    const bool stamp2 = m.n_batch > 1 && !ctxt && (tile == 0 || tile == n_tiles - 1);
+    const int slot2 = tile == 0 ? 640 : 648;
+#endif
+    GFK_STAMP_IF(m, stamp2, slot2);
+    // ---- staging, one global round: every load whose address needs no other load is issued
+    //      before the first wait.  Issue order matters (vmcnt counts in order): the rows' tile
+    //      extents first, so the dependent first-non-zero loads wait for them alone while
+    //      dz0 and the block's p / m / v stay in flight ----
+    const int nb = *nbp;
+    if (H0P > 64) {             // wide layers: dz0 staged ahead of the round (its guarded loads in
+      for (int i = tid; i < B * H0P; i += UT) {   // a loop would make every later wait a full one)
+        const int r = i / H0P, c = i % H0P;
+        dz[r * ZS + c] = (c < H0 && r < nb) ? dz0[r * H0 + c] : 0.f;
+      }
+    }
+    // 16 threads per row: the row's non-zeros inside this tile (rows tid/16 + 32 i,
+    // i < B / 32).  Unconditional loads of clamped rows (the table has bmax rows; a contextual
+    // tile reads column 0 and drops it): behind `r < nb` they would wait for nb's round trip
+    constexpr int XR = 128 / (UT / 16);          // row slots per thread (bmax <= 128)
+    const int row = tid >> 4, sub = tid & 15;
+    int xe0[XR], xe1[XR];
+#pragma unroll
+    for (int i = 0; i < XR; ++i) {
+      const int r = min(row + i * (UT / 16), B - 1);
+      const unsigned ts = 4u * (unsigned)(r * (n_tiles + 1) + (ctxt ? 0 : tile));   // (bytes: 4 B n_tiles)
+      xe0[i] = at32(tstart, ts);
+      xe1[i] = at32(tstart, ts + 4u);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    // dz0 rows tid / 64 + UW u, column tid % 64 (H0P <= 64; no runtime division): clamped,
+    // unconditional (wider layers drop them: no branch between the loads of this round),
+    // DZU rows per thread in flight (128 rows at 8 waves: two chunks)
+    constexpr int DZU = 8;
+    const int zc = tid & 63;
+    float dzr[DZU];
+    auto dz_issue = [&](int r0) {
+#pragma unroll
+      for (int u = 0; u < DZU; ++u) {
+        const int r = min(r0 + (tid >> 6) + UW * u, B - 1);
+        dzr[u] = at32(dz0, 4u * (unsigned)(r * H0 + min(zc, H0 - 1)));
+      }
+    };
+    auto dz_store = [&](int r0) {
+#pragma unroll
+      for (int u = 0; u < DZU; ++u) {
+        // an integer mask, not a select (a select lets the compiler sink the load into a
+        // branch + vmcnt(0) each; 0 * x would keep a NaN of the rows past nb)
+        // (the value is waited for by every lane, ahead of the guarded store: a wait inside
+        // the branch leaves the load "maybe pending" for the wait-count pass on the other path)
+        const int r = r0 + (tid >> 6) + UW * u;
+        const unsigned keepm = (zc < H0 && r < nb) ? ~0u : 0u;
+        asm volatile("" : "+v"(dzr[u]));
+        if (zc < H0P && r < B) dz[r * ZS + zc] = __uint_as_float(__float_as_uint(dzr[u]) & keepm);
+      }
+    };
+    dz_issue(0);
+    __builtin_amdgcn_sched_barrier(0);
+    // rows >= nb carry an earlier batch's extents (or none): masked AFTER the load, so nothing
+    // behind a dead row is dereferenced; then each row slot's first (index, value) pair,
+    // clamped into the row's extent (an empty extent reads a neighbouring entry and drops it)
+    int xc[XR];
+    float xv[XR];
+#pragma unroll
+    for (int i = 0; i < XR; ++i) {
+      const int r = row + i * (UT / 16);
+      const int live = (!ctxt && r < nb && r < B) ? -1 : 0;
+      xe0[i] &= live;
+      xe1[i] &= live;
+    }
+#pragma unroll
+    for (int i = 0; i < XR; ++i) {               // (a contextual tile reads entry 0 and drops it)
+      const unsigned e = (unsigned)min(xe0[i] + sub, max(xe1[i] - 1, 0));
+      xc[i] = indices[e];
+      xv[i] = values[e];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    GFK_STAMP_IF(m, stamp2, slot2 + 1);
+    // ---- LDS: dz0 rows (zero padding).  Ahead of the p / m / v prefetch: it waits for dz0
+    //      alone (the first-non-zero pairs behind it stay in flight) and frees its registers
+    //      before the prefetch takes 24 -- the prefetch starts one L2 round trip later ----
+    if (H0P <= 64) {
+      dz_store(0);
+      for (int r0 = DZU * UW; r0 < B; r0 += DZU * UW) {
+        dz_issue(r0);
+        dz_store(r0);
+      }
+    }
+    // (the round's loads so far are common to both layouts and issued once, ahead of the split)
+    auto body = [&](auto flat_c) {
+    constexpr bool flat = decltype(flat_c)::value;
+    // prefetch the optimizer state of this lane's outputs: subtiles t = wave + UW u
+    // (16x16 each; H0 <= 64 -> at most 16 subtiles, one pass; wider layers take passes
+    // of UW * PU subtiles below, the later ones prefetched after the scatter)
+    constexpr int PU = 16 / UW;
+    float pp[PU][4], pm[PU][4], pv[PU][4];
+    constexpr int FQ = 64 * 64 / 4 / UT;         // quads per thread (H0 <= 64)
+    static_assert(FQ <= PU, "flat epilogue reuses the prefetch registers");
+    if (flat) {
+      // unconditional, clamped quads (threads past the block re-read its last quad and drop
+      // it; gradient mode reads the parameter three times): no select on a pending load
+      const int64_t om = fused ? m.off_m : 0, ov = fused ? m.off_v : 0;
+#pragma unroll
+      for (int u = 0; u < FQ; ++u) {
+        const unsigned e = 4u * (unsigned)min(4 * (tid + UT * u), nel - 4);      // (bytes: <= 16 KiB)
+        const f32x4 a = at32((gq_t)wblk, e), b = at32((gq_t)(wblk + om), e), c = at32((gq_t)(wblk + ov), e);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { pp[u][i] = a[i]; pm[u][i] = b[i]; pv[u][i] = c[i]; }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < PU; ++u) {
+      if (flat) break;
+      const int t = wave + UW * u;
+      const int i0 = (t / NT) * 16, j0 = (t % NT) * 16;
+      const int j = min(j0 + (lane & 15), H0 - 1);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int v = min(c0 + i0 + (lane >> 4) * 4 + r, V - 1);
+        gf_t p = w_in + (size_t)v * H0 + j;
+        pp[u][r] = pm[u][r] = pv[u][r] = 0.f;
+        if (t < MT * NT && fused) {
+          pp[u][r] = *p;
+          pm[u][r] = p[m.off_m];
+          pv[u][r] = p[m.off_v];
+        }
+      }
+    }
+    // ---- LDS: the x^T tile zeroed (contextual tiles: filled) ----
+    if (zs) {                   // x_ctx^T tile: the batch rows' contextual features
+      for (int i = tid; i < B * 64; i += UT) {
+        const int b = i >> 6, v = i & 63;
+        xt[v * XS + b] = (b < nb && c0 + v < V) ? m.ctx[(size_t)m.ws_doc[b] * V + c0 + v] : 0.f;
+      }
+    } else if (ctxt) {          // A^T tile: the adapted rows (slab 0 of ctx_fwd's output)
+      const float* ag = m.ws_actx + (size_t)tile * B * 64;
+      for (int i = tid; i < B * 64; i += UT) {
+        const int b = i >> 6, v = i & 63;
+        xt[v * XS + b] = b < nb ? ag[i] : 0.f;
+      }
+    } else {
+      for (int i = tid; i < 64 * XS; i += UT) xt[i] = 0.f;
+    }
+    // (staged global data reaches LDS through registers, whose loads the compiler waits for:
+    // both barriers order LDS traffic only, and p / m / v stay in flight across them)
+    lds_barrier();              // the zero fill is done before the scatter
+    GFK_STAMP_IF(m, stamp2, slot2 + 2);
+#pragma unroll
+    for (int i = 0; i < XR; ++i) asm volatile("" : "+v"(xc[i]), "+v"(xv[i]));   // (as for dz0 above)
+#pragma unroll
+    for (int i = 0; i < XR; ++i) {
+      const int r = row + i * (UT / 16);
+      // the preloaded pair is the row slot's first entry; a tile holds more than 16
+      // non-zeros of a row rarely (~2 per row per tile at V = 4.7k)
+      for (int k = 0, e = xe0[i] + sub; e < xe1[i]; ++k, e += 16) {
+        const int c = (k == 0 ? xc[i] : indices[e]) - c0;
+        xt[c * XS + r] = k == 0 ? xv[i] : values[e];
+      }
+    }
+    lds_barrier();
+
+    GFK_STAMP_WG(m, !ctxt && tile == 0, 41);
+    GFK_STAMP_IF(m, stamp2, slot2 + 3);
+    // ---- G[v, j] = sum_b xt[v, b] dz[b, j] and the update ----
+    const AdamCoef ac = adam_coef(m);
+    const bool sh = is_shared(m, w_in_flat);
+    f32x4 gk[PU];
+    for (int pass = 0; pass * UW * PU < MT * NT; ++pass) {
+    if (pass > 0) {             // wide input layers (H0 > 64): the next subtiles' state
+#pragma unroll
+      for (int u = 0; u < PU; ++u) {
+        const int t = pass * UW * PU + wave + UW * u;
+        const int i0 = (t / NT) * 16, j0 = (t % NT) * 16;
+        const int j = min(j0 + (lane & 15), H0 - 1);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int v = min(c0 + i0 + (lane >> 4) * 4 + r, V - 1);
+          gf_t p = w_in + (size_t)v * H0 + j;
+          pp[u][r] = pm[u][r] = pv[u][r] = 0.f;
+          if (t < MT * NT && fused) {
+            pp[u][r] = *p;
+            pm[u][r] = p[m.off_m];
+            pv[u][r] = p[m.off_v];
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < PU; ++u) {
+      const int t = pass * UW * PU + wave + UW * u;
+      if (t >= MT * NT) break;
+      const int i0 = (t / NT) * 16, j0 = (t % NT) * 16;
+      const float* ap = xt + (i0 + (lane & 15)) * XS + (lane >> 4);
+      const float* bp = dz + (lane >> 4) * ZS + j0 + (lane & 15);
+      f32x4 c0v = {0.f, 0.f, 0.f, 0.f}, c1v = {0.f, 0.f, 0.f, 0.f};
+      for (int k = 0; k < B; k += 8) {
+        c0v = mfma16x16x4(ap[k], bp[k * ZS], c0v);
+        c1v = mfma16x16x4(ap[k + 4], bp[(k + 4) * ZS], c1v);
+      }
+      const f32x4 g = c0v + c1v;
+      const int j = j0 + (lane & 15);
+      if (flat) {               // park the gradient in registers until every wave is done
+        gk[u] = g;
+        continue;
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int v = c0 + i0 + (lane >> 4) * 4 + r;
+        if (v >= V || j >= H0) continue;
+        gf_t p = w_in + (size_t)v * H0 + j;
+        if (!fused) {
+          p[m.off_g] = g[r];
+        } else {
+          float mo = pm[u][r], vo = pv[u][r];
+          float np = adam_update(pp[u][r], g[r], mo, vo, ac);
+          if (sh && m.fed_scale_on) np *= m.fed_scale;
+          p[m.off_m] = mo;
+          p[m.off_v] = vo;
+          p[gfk_own<GB>(m)] = np;
+        }
+      }
+    }
+    }
+    if (flat) {
+      // the gradient tile [64, H0] into x^T's buffer in the block's own (flat) order
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < PU; ++u) {
+        const int t = wave + UW * u;
+        if (t >= MT * NT) break;
+        const int i0 = (t / NT) * 16, j0 = (t % NT) * 16, j = j0 + (lane & 15);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (j < H0) xt[(i0 + (lane >> 4) * 4 + r) * H0 + j] = gk[u][r];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < FQ; ++u) {
+        const int e = 4 * (tid + UT * u);
+        if (e >= nel) break;
+        const f32x4 g = *reinterpret_cast<const f32x4*>(xt + e);
+        f32x4 np, mo, vo;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          float a = pm[u][i], b = pv[u][i];
+          float x = fused ? adam_update(pp[u][i], g[i], a, b, ac) : g[i];
+          np[i] = sh && m.fed_scale_on && fused ? x * m.fed_scale : x;
+          mo[i] = a;
+          vo[i] = b;
+        }
+        auto st4 = [&](gf_t q, const f32x4& x) {
+          if (al4 && e + 3 < nel) { *(gq_t)(q + e) = x; return; }
+#pragma unroll
+          for (int i = 0; i < 4; ++i) if (e + i < nel) q[e + i] = x[i];
+        };
+        if (!fused) {
+          st4(wblk + m.off_g, np);
+        } else {
+          st4(wblk + m.off_m, mo);
+          st4(wblk + m.off_v, vo);
+          st4(wblk + gfk_own<GB>(m), np);
+        }
+      }
+    }
+    GFK_STAMP_WG(m, !ctxt && tile == 0, 42);
+    GFK_STAMP_IF_VM(m, stamp2, slot2 + 4);
+    };
+    // (the subtile layout ends the kernel in its own branch: nothing of it is pending where the
+    // flat layout starts)
+    if (!flat_rt) {
+      body(std::false_type{});
+      return;
+    }
+    body(std::true_type{});
   }
-  GFK_STAMP(m, 42);
 }
 
 // The large-batch plan's dense W_in tile (bmax > 128, gradient mode, H0 <= 64): the W_in
@@ -971,13 +1336,14 @@ static bool win_sparse_vl(const GfkModel* m) {
 // The instance table (csrc/gfk_launch.h): the launcher looks its kernel up by the key it
 // computes from the model, and gfk_win_update_set_smem raises the dynamic-LDS limit of the
 // same rows.  A new instance is one new row.
-// {kernel, threads} the dense tiles | {kernel, LDS second moment, contextual tiles, large batch}
+// {kernel, threads, waves per SIMD where not the shape's own} the dense tiles | {kernel, LDS second moment, contextual tiles, large batch}
 // the sparse tiles | {kernel} the large-batch chunked dense tiles (one client)
 enum { WINK_DENSE, WINK_SPARSE, WINK_LB };
 #define WIN_SPARSE_ROW(VL, CTX) {{WINK_SPARSE, VL, CTX}, {gfk_win_sparse_k<512, false, VL, CTX>, gfk_win_sparse_k<512, true, VL, CTX>}}
 static const GfkRowU kWinUpdate[] = {
     {{WINK_DENSE, 512}, GFK_PAIR(gfk_win_update_k, 512)},
     {{WINK_DENSE, 1024}, GFK_PAIR(gfk_win_update_k, 1024)},
+    {{WINK_DENSE, 512, 6}, {nullptr, gfk_win_update_k<512, true, 6>}},
     WIN_SPARSE_ROW(false, false), WIN_SPARSE_ROW(true, false), WIN_SPARSE_ROW(false, true), WIN_SPARSE_ROW(true, true),
     {{WINK_SPARSE, 0, 0, 1}, {gfk_win_sparse_k<512, false, false, false, GFK_BMAX_LIMIT / 64>,
                               gfk_win_sparse_k<512, true, false, false, GFK_BMAX_LIMIT / 64>}},
@@ -1009,7 +1375,11 @@ extern "C" int gfk_launch_win_update(const GfkModel* m, const GfkUpdate* u, hipS
   // batched launch of several clients' tiles asks for the 8-wave shape (stage_flags bit 9,
   // set by BatchedSteps when all clients' tiles together exceed two rounds)
   const int nt = ((m->n_tiles > 2 * m->dec_grid && m->n_tiles > 512) || (m->stage_flags & WIN_BATCH8)) ? 512 : 1024;
-  return gfk_launch(gfk_find(kWinUpdate, WINK_DENSE, nt), m, u, g, dim3(nt), sm, s);
+  // (stage_flags GFK_WIN_WAVES6 asks for the 6-waves-per-SIMD instance of the 8-wave shape: a
+  // launch it has no instance for is an error, never the other instance)
+  const int wps = (m->stage_flags & GFK_WIN_WAVES6) ? 6 : 0;
+  if (wps && nt != 512) return -1;
+  return gfk_launch(gfk_find(kWinUpdate, WINK_DENSE, nt, wps), m, u, g, dim3(nt), sm, s);
 }
 
 extern "C" int gfk_win_update_set_smem(size_t bytes) {

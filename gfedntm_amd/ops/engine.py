@@ -72,8 +72,11 @@ STAGE_POST_ROWS2 = abi.POST_ROWS2  # bit 20: batched post_bwd, two rows per work
 STAGE_POST_JOINT = abi.POST_JOINT  # bit 21: ... the rows through each phase together (with bit 20)
 STAGE_POST_ROWS4 = abi.POST_ROWS4  # bit 22: ... four rows per workgroup (with bits 20 and 21)
 STAGE_BWD_BATCH8 = abi.BWD_BATCH8  # bit 23: batched ProdLDA tile backward, 8-wave workgroups, three per CU
+STAGE_WIN_WAVES6 = abi.WIN_WAVES6  # bit 24: batched win_update (with bit 9), 6 waves per SIMD, three per CU
 # the LDS one of a CU's three 8-wave backward workgroups may take (csrc/prodlda.hip BWD8_LDS)
 BWD8_LDS = LDS_LIMIT // 3
+# ... and one of its three 6-waves-per-SIMD win_update workgroups
+WIN6_LDS = LDS_LIMIT // 3
 # the shape GFEDNTM_POST_ROWS=auto takes where bit 20 applies (a key of abi.POST_ROWS_SHAPES):
 # the headline's interleaved A/B, 8 clients K = 50 (profiles/r7/ab_post_rows.txt): serial2
 # 0.1176 ms per round, two joint rows 0.1159, four 0.1193
@@ -133,6 +136,36 @@ def bwd_batch8_flag(n_clients: int, n_tiles: int, cus: int, *, bmax: int, K: int
                                "(one-range fp32 tile backward, bmax 64, K <= 64, LDS <= %d B)" % BWD8_LDS)
         return STAGE_BWD_BATCH8
     return STAGE_BWD_BATCH8 if exists and 2 * cus < n_clients * n_tiles <= 3 * cus else 0
+
+
+def win_waves_flag(n_clients: int, n_wg: int, cus: int, *, dense: bool, batch8: bool, fused: bool,
+                   H0: int, lds_bytes: int, knob: str = "auto") -> int:
+    """stage_flags bits of a batched launch's win_update register budget (GFEDNTM_WIN_WAVES).
+
+    The 8-wave dense tile kernel (stage bit 9) is compiled for 8 waves per SIMD (64 VGPRs,
+    which it exceeds: it spills) and, as a second instance (bit 24), for 6 (80 VGPRs, three
+    workgroups per CU).  That instance exists for launches of M > 1 clients whose W_in
+    gradient runs as dense tiles (``dense``: no sparse tiles, not the large-batch plan), with
+    fused updates, H0 <= 64, within a third of a CU's LDS.  ``n_wg``: a client's workgroups
+    (tiles, contextual tiles, weight and vector jobs, the next-batch workgroup).  ``auto``:
+    bit 24 where the launch takes the 8-wave shape anyway (``batch8``) and three workgroups
+    per CU hold every client's at once (M n_wg <= 3 CUs), so the lower occupancy costs no
+    second round.  ``6`` / ``8`` force the 8-wave shape at that budget on every launch of
+    M > 1 clients with dense tiles (bit 9, and bit 24 for ``6``); ``6`` without an instance
+    is an error."""
+    if knob not in ("auto", "8", "6"):
+        raise ValueError(f"GFEDNTM_WIN_WAVES={knob!r}: expected auto, 8 or 6")
+    if n_clients < 2:
+        return 0
+    exists = bool(dense) and bool(fused) and H0 <= 64 and lds_bytes <= WIN6_LDS
+    if knob == "8":
+        return STAGE_WIN_BATCH8 if dense else 0
+    if knob == "6":
+        if not exists:
+            raise RuntimeError("GFEDNTM_WIN_WAVES=6: no 6-waves-per-SIMD win_update for this launch "
+                               "(dense W_in tiles, fused updates, H0 <= 64, LDS <= %d B)" % WIN6_LDS)
+        return STAGE_WIN_BATCH8 | STAGE_WIN_WAVES6
+    return STAGE_WIN_WAVES6 if exists and batch8 and n_clients * n_wg <= 3 * cus else 0
 
 
 def engine_bmax(tm) -> int:
@@ -1896,6 +1929,17 @@ class BatchedSteps:
                 kq=bwd_kq(mm.n_tiles, mm.n_dpart, mm.K) if tile_bwd else 0, bwd_pre=mm.bwd_pre,
                 lds_bytes=bwd8_lds_bytes(mm.bmax, mm.K, mm.kt),
                 knob=os.environ.get("GFEDNTM_BWD_WAVES", "auto"))
+            # win_update's 8-wave tile kernel needs more than the 64 VGPRs of 8 waves per SIMD;
+            # at 6 (80 VGPRs) three workgroups share a CU, enough where they hold every
+            # client's tiles and jobs at once.  GFEDNTM_WIN_WAVES = auto | 8 | 6
+            extra = mm.n_tiles if mm.ctx_fused == 1 else -(-mm.C // VB) if mm.ctx_fused == 2 else 0
+            mm.stage_flags |= win_waves_flag(
+                M, mm.n_tiles + extra + e._u.n_w + e._u.n_v + 1, self._cu,
+                dense=not mm.stage_flags & (STAGE_WIN_SPARSE | STAGE_LB) and mm.bmax <= 128,
+                batch8=bool(mm.stage_flags & STAGE_WIN_BATCH8),
+                fused=e.update_mode == UPDATE_FUSED, H0=int(mm.H[0]),
+                lds_bytes=int(e.lib.gfk_smem_required(C.byref(mm), 5)),
+                knob=os.environ.get("GFEDNTM_WIN_WAVES", "auto"))
             uu = e._u
             if self._shared is not None:
                 uu = abi.GfkUpdate.from_buffer_copy(bytes(e._u))
@@ -1926,6 +1970,10 @@ class BatchedSteps:
                 "8 waves" if self._host.stage_flags & STAGE_BWD_BATCH8 else
                 "16 waves" if bwd_kq(self._host.n_tiles, self._host.n_dpart, self._host.K) == 1
                 else "k ranges")
+        if (self._host.stage_flags & STAGE_WIN_BATCH8 and self._host.bmax <= 128
+                and not self._host.stage_flags & (STAGE_WIN_SPARSE | STAGE_LB)):
+            self.plan += "; win_update 8-wave tiles, %d waves per SIMD" % (
+                6 if self._host.stage_flags & STAGE_WIN_WAVES6 else 8)
 
     def prepare(self):
         """Upload the descriptors now (before a capture)."""

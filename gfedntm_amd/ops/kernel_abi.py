@@ -30,6 +30,9 @@ POST_ROWS_SHAPES = {"serial2": POST_ROWS2, "2": POST_ROWS2 | POST_JOINT,
 # stage_flags bit of the batched ProdLDA tile backward in 8-wave workgroups (csrc/gfk_common.h
 # GFK_BWD_BATCH8; ops/engine.py bwd_batch8_flag)
 BWD_BATCH8 = 1 << 23
+# stage_flags bit of the batched win_update's 8-wave dense tiles compiled for 6 waves per SIMD
+# (csrc/gfk_common.h GFK_WIN_WAVES6; ops/engine.py win_waves_flag)
+WIN_WAVES6 = 1 << 24
 
 # phase ids (csrc/step.cpp GfkPhase)
 PH_BATCH_DOCS = 0

@@ -13,7 +13,10 @@ to a travelling path on the GPU box, so the box does not compile)
 with grid z = the clients.  Client 0 alone carries the stamp buffer; of its decoder backward
 the first-tile and the last-tile workgroup are stamped (entry, staged, dense done, end), which
 shows whether the last tiles wait for a second round of workgroups (GFEDNTM_BWD_WAVES picks
-the backward's shape).
+the backward's shape).  Of its win_update likewise the first-tile and the last-tile workgroup
+(entry, tile extents landed, first barrier passed, scatter done, end), and entry and end of the
+first weight job, the last vector job and the next-batch workgroup, all on the chip-wide clock
+(GFEDNTM_WIN_WAVES picks the tile kernel's register budget).
 
 usage: python tools/stamps.py [--topics K] [--vocab V] [--hidden 50,50] [--batch B]
                               [--nnz N] [--docs D] [--steps S] [--clients M]
@@ -65,12 +68,13 @@ def batched(a, kw):
     tms[0].engine._m.dbg = dbg.data_ptr()
     bs = BatchedSteps([t.engine for t in tms])
     bs.prepare()
-    rows = []
+    rows, wins = [], []
     for s in range(a.steps):
         dbg.zero_()
         bs.launch()
         torch.cuda.synchronize()
         rows.append(dbg[600:616].cpu().numpy().reshape(2, 8)[:, :4].copy())
+        wins.append(dbg[640:664].cpu().numpy().copy())
     m = bs._host
     print(f"clients={a.clients} K={a.topics} V={a.vocab} tiles={m.n_tiles} n_dpart={m.n_dpart} "
           f"stage_flags={m.stage_flags} plan: {bs.plan}")
@@ -82,6 +86,18 @@ def batched(a, kw):
         t0 = r[0, 0]
         print(f"  step {s}: first tile " + " ".join("%.2f" % ((int(v) - int(t0)) / 100) for v in r[0]) +
               " | last tile " + " ".join("%.2f" % ((int(v) - int(t0)) / 100) for v in r[1]))
+    # win_update (csrc/update.hip gfk_win_update_k, dbg slots 640 / 648 the first-tile and the
+    # last-tile workgroup, 656 / 658 / 660 the first weight job, the last vector job and the
+    # next-batch workgroup); end stamps are taken once the wave's stores have completed
+    print("win_update, client 0, microseconds (s_memrealtime) from the earliest stamped entry: "
+          "tiles entry, extents landed, first barrier passed, scatter done, end; jobs entry, end")
+    for s, w in enumerate(wins):
+        if s < a.steps - 5:
+            continue
+        t0 = min(int(v) for v in w if v)
+        us = lambda vs: " ".join("%.2f" % ((int(v) - t0) / 100) if v else "-" for v in vs)
+        print(f"  step {s}: first tile {us(w[0:5])} | last tile {us(w[8:13])} | weight job 0 "
+              f"{us(w[16:18])} | last vector job {us(w[18:20])} | next batch {us(w[20:22])}")
 
 
 def main(argv=None):
