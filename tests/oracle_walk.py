@@ -12,7 +12,8 @@ and the kernel must stay within 8 e_fp32 + 4 ulp(scale) (docs/PARITY.md section 
 ratios measured on the GPU).
 
 tests/test_oracle_walk.py pins the oracle to avitm_loss_explicit on the CPU;
-tests/test_epoch_walk_gpu.py runs the walks.
+tests/test_epoch_walk_gpu.py runs the walks.  tests/fused_walk.py is the same walk for the fused
+update mode (no gradients: the new moments and parameters) and for batched client launches.
 """
 import copy
 from collections import defaultdict
@@ -114,6 +115,9 @@ def tensor_class(name):
     """The row of the parity table a compared tensor belongs to."""
     if name in ("loss", "kl", "rl"):
         return name
+    for cls in ("adam m", "adam v", "adam p"):      # the fused walk (tests/fused_walk.py)
+        if name.startswith(cls + " "):
+            return cls
     if "running" in name:
         return "bn beta" if name.startswith("beta_batchnorm") else "bn heads"
     if name in NOISE_KEYS:
@@ -133,7 +137,7 @@ class Parity:
 
     def __init__(self, case=""):
         self.case = case
-        self.worst = defaultdict(lambda: {"ratio": 0.0, "use": 0.0})
+        self.worst = defaultdict(lambda: {"ratio": 0.0, "use": 0.0, "at": ""})
         self.failures = []
 
     def check(self, step, name, kernel, f64, f32, scale=None, cap=None):
@@ -151,13 +155,32 @@ class Parity:
         w = self.worst[tensor_class(name)]
         if e_32 > 0:
             w["ratio"] = max(w["ratio"], e_k / e_32)
-        w["use"] = max(w["use"], e_k / bound if bound > 0 else (0.0 if e_k == 0 else float("inf")))
+        use = e_k / bound if bound > 0 else (0.0 if e_k == 0 else float("inf"))
+        if use > w["use"]:
+            w["use"], w["at"] = use, f"step {step} {name}"
         if over:
             self.failures.append(f"step {step} {name}: e_kernel {e_k:.3e} > bound {bound:.3e} "
                                  f"(e_fp32 {e_32:.3e}, scale {scale:.3e}, cap {cap})")
 
+    def check_elementwise(self, step, name, kernel, ref, bound):
+        """|kernel - ref| <= bound, element by element (``bound`` a float64 tensor derived from
+        the arithmetic under test: no fp32 error to measure it against, so no ratio)."""
+        err = (kernel.double() - ref.double()).abs()
+        use = torch.where(bound > 0, err / bound.clamp_min(1e-300),
+                          torch.where(err > 0, torch.full_like(err, float("inf")), torch.zeros_like(err)))
+        worst = float(use.max()) if use.numel() else 0.0
+        w = self.worst[tensor_class(name)]
+        if worst > w["use"]:
+            w["use"], w["at"] = worst, f"step {step} {name}"
+        if not worst <= 1.0:
+            i = int(use.flatten().argmax())
+            self.failures.append(f"step {step} {name}: |kernel - ref| {float(err.flatten()[i]):.3e} > bound "
+                                 f"{float(bound.flatten()[i]):.3e} at element {i} (ref "
+                                 f"{float(ref.flatten()[i]):.6e}), {int((use > 1).sum())} of {use.numel()} over")
+
     def lines(self):
         return [f"PARITY {self.case} | {c} | e_kernel/e_fp32 {w['ratio']:.2f} | bound used {w['use']:.3f}"
+                f" ({w['at']})"
                 for c, w in sorted(self.worst.items())]
 
 
