@@ -38,6 +38,28 @@
 //   gfk_score_mean_k   RL[d] = mean over the draws' rows, in draw order.
 //
 // Always fp32 (scoring is a measurement), no atomics, fixed-order reductions.
+//
+// The NeuralLDA decoder and the label head (gfk_score_ext, second half of this file) reuse
+// gfk_score_theta_k -- the same theta workspace and draw keys -- and add:
+//
+//   gfk_lda_topic_lse_k      L[k] = log sum_v exp(zn[k, v]), zn = (beta - rm) rsqrt(rv + eps):
+//                            once per score call; (topic, vocabulary range) work items,
+//                            lanes on consecutive columns (16 B per lane where the rows
+//                            are 16-byte aligned), a per-lane online (max, sum) pair merged
+//                            lanes -> waves -> (gfk_lda_topic_lse_fin_k) ranges in range
+//                            order.  LDS: 32 B.
+//   gfk_lda_sparse_k<G>      one wave per document: p[r, v] = sum_k theta[r, k]
+//                            exp(zn[k, v] - L[k]) at the document's non-zeros alone, one exp
+//                            per (non-zero, k) shared by a group of G draws (G = 1 for
+//                            n_samples <= 1, else 4).  LDS per workgroup of 4 waves:
+//                            theta [4][256 G] + L [4][256] floats = 8 KiB (G = 1) /
+//                            20 KiB (G = 4).  K <= 256.
+//   gfk_label_ce_k           one wave per row: logits = theta w_cls^T + b_cls, CE = lse -
+//                            logit[argmax(labels)] (lowest index of the maximum).  LDS 4 KiB.
+//                            K <= 256, L <= 256.
+//   gfk_score_finish_k       out[d] = (KL, RL[, CE]): the draws' means in draw order.
+//
+// No normalised [K, V] matrix and no [rows, V] array exist.
 #include "gfk_common.h"
 
 using namespace gfk;
@@ -430,5 +452,331 @@ extern "C" int gfk_doc_score(const GfkModel* m, const GfkScore* p, hipStream_t s
   if (rc) return rc;
   hipLaunchKernelGGL(gfk_score_mean_k, dim3((p->n_docs + SC_THREADS - 1) / SC_THREADS), dim3(SC_THREADS), 0,
                      s, *p);
+  return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// NeuralLDA decoder (reference decoder_network.py:121-127 in eval mode) and the label head
+// (inference_network.py label_classification; avitm.py / ctm.py add its cross-entropy).
+//
+//   zn[k, v] = (beta[k, v] - rm[v]) rsqrt(rv[v] + bn_eps)
+//   L[k]     = log sum_{v < V} exp(zn[k, v])               max-shifted: zn is unbounded
+//   p[r, v]  = sum_k theta[r, k] exp(zn[k, v] - L[k])      every factor <= 1
+//   RL[r]    = - sum_{v in nz(d)} x_v log(p[r, v] + 1e-10)
+//   CE[r]    = lse(theta[r] w_cls^T + b_cls) - logit[argmax labels[d]]
+extern "C" {
+typedef struct GfkScoreX {
+  GfkScore s;              // as for gfk_doc_score, but s.out is a WORKSPACE [n_docs, 2]: the
+                           // theta kernel's KL and the ProdLDA decoder's RL land there
+                           // (NeuralLDA does not read s.lse_part)
+  const float* labels;     // [n_docs, L] the chunk's label rows; null: no CE column
+  const float* topic_lse;  // [K] gfk_lda_topic_lse's L (NeuralLDA)
+  float* ce_rows;          // workspace [n_docs * R] (label head)
+  float* out;              // [n_docs, ncol] = (KL, RL[, CE])
+  int32_t ncol, reserved;  // 2, or 3 with labels
+} GfkScoreX;
+}
+
+namespace {
+
+constexpr int LS_KMAX = 256;                 // topics of the NeuralLDA / label kernels
+constexpr int TL_VEC = 4;                    // columns per lane and pass of the topic lse
+constexpr int TL_STEP = SC_THREADS * TL_VEC;
+
+struct TopicLseArgs {
+  const float *beta, *rm, *rv;
+  float *part, *lse;       // [NV, K, 2] (max, sum exp) partials; [K]
+  int V, K, ldb, vec;      // vec: rows and statistics 16-byte aligned
+  float bn_eps;
+};
+
+// Work item = (topic, vocabulary range), ranges fastest.  Thread t owns columns
+// c_lo + 4 t .. + 3, + 1024, ...: the ownership -- and so every bit of the result -- is
+// the same whether the four columns arrive as one 16-byte load or as four.
+__global__ void __launch_bounds__(SC_THREADS) gfk_lda_topic_lse_k(TopicLseArgs a) {
+  __shared__ float pm[SC_WAVES], ps[SC_WAVES];
+  const int tid = threadIdx.x, lane = tid & 63, wave = uniform(tid >> 6);
+  const int V = a.V, K = a.K;
+  const int n_tiles = (V + SC_VB - 1) / SC_VB;
+  const int NV = sc_vranges(V), tiles_per_range = (n_tiles + NV - 1) / NV;
+  const float bn_eps = a.bn_eps;
+  for (int item = blockIdx.x; item < K * NV; item += gridDim.x) {
+    const int k = item / NV, vr = item - k * NV;
+    const int c_lo = min(vr * tiles_per_range * SC_VB, V);
+    const int c_hi = min(c_lo + tiles_per_range * SC_VB, V);
+    const float* brow = a.beta + (size_t)k * a.ldb;
+    float m = -INFINITY, s = 0.f;
+    for (int c = c_lo + TL_VEC * tid; c < c_hi; c += TL_STEP) {
+      float b[TL_VEC], rm[TL_VEC], rv[TL_VEC];
+      if (a.vec && c + TL_VEC <= c_hi) {
+        const float4 b4 = *reinterpret_cast<const float4*>(brow + c);
+        const float4 m4 = *reinterpret_cast<const float4*>(a.rm + c);
+        const float4 v4 = *reinterpret_cast<const float4*>(a.rv + c);
+        b[0] = b4.x; b[1] = b4.y; b[2] = b4.z; b[3] = b4.w;
+        rm[0] = m4.x; rm[1] = m4.y; rm[2] = m4.z; rm[3] = m4.w;
+        rv[0] = v4.x; rv[1] = v4.y; rv[2] = v4.z; rv[3] = v4.w;
+      } else {
+#pragma unroll
+        for (int i = 0; i < TL_VEC; ++i) {
+          const int ci = min(c + i, c_hi - 1);
+          b[i] = brow[ci];
+          rm[i] = a.rm[ci];
+          rv[i] = a.rv[ci];
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < TL_VEC; ++i) {
+        if (c + i < c_hi) {
+          const float zn = (b[i] - rm[i]) * rsqrtf(rv[i] + bn_eps);
+          const float d = zn - m;
+          const float ex = __expf(-fabsf(d));
+          s = d > 0.f ? s * ex + 1.f : s + ex;
+          m = fmaxf(m, zn);
+        }
+      }
+    }
+    wave_lse(m, s);
+    if (lane == 0) { pm[wave] = m; ps[wave] = s; }
+    lds_barrier();
+    if (tid == 0) {
+#pragma unroll
+      for (int w = 1; w < SC_WAVES; ++w) lse_merge(m, s, pm[w], ps[w]);
+      float* o = a.part + ((size_t)vr * K + k) * 2;
+      o[0] = m;
+      o[1] = s;
+    }
+    lds_barrier();                           // pm / ps are rewritten by the next item
+  }
+}
+
+__global__ void __launch_bounds__(SC_THREADS) gfk_lda_topic_lse_fin_k(TopicLseArgs a) {
+  const int k = blockIdx.x * SC_THREADS + threadIdx.x;
+  if (k >= a.K) return;
+  const int NV = sc_vranges(a.V);
+  float m = -INFINITY, s = 0.f;
+  for (int vr = 0; vr < NV; ++vr) {
+    const float* o = a.part + ((size_t)vr * a.K + k) * 2;
+    lse_merge(m, s, o[0], o[1]);
+  }
+  a.lse[k] = m + __logf(s);
+}
+
+// One wave per document; the draws in groups of G.  th[k][g]: the group's theta (zero rows
+// past the last draw), so one topic's G factors are one LDS read; lw[k] = L[k].  Each lane
+// takes non-zeros e0 + lane, + 64, ...: K scattered loads of beta's column (stride ldb), one
+// exp each, G multiply-adds.  (zn is the expression of gfk_lda_topic_lse_k, bit for bit.)
+template <int G>
+__global__ void __launch_bounds__(SC_THREADS) gfk_lda_sparse_k(ScoreArgs a, GfkScore p,
+                                                               const float* __restrict__ topic_lse) {
+  __shared__ __attribute__((aligned(16))) float ths[SC_WAVES][LS_KMAX * G];
+  __shared__ float lws[SC_WAVES][LS_KMAX];
+  const int lane = threadIdx.x & 63, wave = uniform(threadIdx.x >> 6);
+  const int K = a.K, ldb = a.ldb;
+  const int R = p.n_samples > 0 ? p.n_samples : 1;
+  const float bn_eps = a.bn_eps;
+  float* th = ths[wave];
+  float* lw = lws[wave];
+  for (int k = lane; k < K; k += 64) lw[k] = topic_lse[k];
+  for (int d = blockIdx.x * SC_WAVES + wave; d < p.n_docs; d += gridDim.x * SC_WAVES) {
+    const int e0 = p.indptr[d], e1 = p.indptr[d + 1];
+    for (int s0 = 0; s0 < R; s0 += G) {
+      __builtin_amdgcn_wave_barrier();       // (the previous group's reads of th are done)
+      for (int k = lane; k < K; k += 64) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          const int s = min(s0 + g, R - 1);
+          const float v = p.theta[((size_t)d * R + s) * K + k];
+          th[k * G + g] = s0 + g < R ? v : 0.f;
+        }
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the wave's theta group is in LDS
+      __builtin_amdgcn_wave_barrier();
+      float t[G];
+#pragma unroll
+      for (int g = 0; g < G; ++g) t[g] = 0.f;
+      for (int e = e0 + lane; e < e1; e += 64) {
+        const int v = p.indices[e];
+        const float x = p.values[e];
+        const float rm = a.beta_rm[v], rs = rsqrtf(a.beta_rv[v] + bn_eps);
+        const float* bc = a.beta + v;
+        float pr[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) pr[g] = 0.f;
+#pragma unroll 4
+        for (int k = 0; k < K; ++k) {
+          const float zn = (bc[(size_t)k * ldb] - rm) * rs;
+          const float ex = __expf(zn - lw[k]);
+#pragma unroll
+          for (int g = 0; g < G; ++g) pr[g] += th[k * G + g] * ex;
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g) t[g] += x * __logf(pr[g] + 1e-10f);
+      }
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        const float tg = wave_sum(t[g]);
+        if (lane == 0 && s0 + g < R) p.rl_rows[(size_t)d * R + s0 + g] = -tg;
+      }
+    }
+  }
+}
+
+// One wave per row; lane l owns labels l, l + 64, l + 128, l + 192.
+__global__ void __launch_bounds__(SC_THREADS) gfk_label_ce_k(ScoreArgs a, GfkScore p,
+                                                             const float* __restrict__ labels,
+                                                             const float* __restrict__ w_cls,
+                                                             const float* __restrict__ b_cls,
+                                                             float* __restrict__ ce_rows, int L) {
+  __shared__ float ts[SC_WAVES][LS_KMAX];
+  constexpr int LQ = 4;
+  const int lane = threadIdx.x & 63, wave = uniform(threadIdx.x >> 6);
+  const int K = a.K;
+  const int R = p.n_samples > 0 ? p.n_samples : 1;
+  const int n_rows = p.n_docs * R;
+  float* trow = ts[wave];
+  float bias[LQ];
+#pragma unroll
+  for (int q = 0; q < LQ; ++q) bias[q] = b_cls[min(lane + 64 * q, L - 1)];
+  for (int row = blockIdx.x * SC_WAVES + wave; row < n_rows; row += gridDim.x * SC_WAVES) {
+    __builtin_amdgcn_wave_barrier();         // (the previous row's reads of trow are done)
+    for (int k = lane; k < K; k += 64) trow[k] = p.theta[(size_t)row * K + k];
+    // the target: the lowest index of the label row's maximum
+    const float* lab = labels + (size_t)(row / R) * L;
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+#pragma unroll
+    for (int q = 0; q < LQ; ++q) {
+      const int l = lane + 64 * q;
+      const float v = lab[min(l, L - 1)];
+      if (l < L && v > bv) { bv = v; bi = l; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // the wave's theta row is in LDS
+    __builtin_amdgcn_wave_barrier();
+    float z[LQ], mx = -INFINITY, zt = 0.f;
+#pragma unroll
+    for (int q = 0; q < LQ; ++q) {
+      const int l = lane + 64 * q;
+      const float* wr = w_cls + (size_t)min(l, L - 1) * K;
+      float acc = bias[q];
+      for (int k = 0; k < K; ++k) acc += trow[k] * wr[k];
+      z[q] = l < L ? acc : -INFINITY;
+      mx = fmaxf(mx, z[q]);
+      zt += l == bi ? acc : 0.f;
+    }
+    mx = wave_max(mx);
+    float sum = 0.f;
+#pragma unroll
+    for (int q = 0; q < LQ; ++q) sum += lane + 64 * q < L ? __expf(z[q] - mx) : 0.f;
+    sum = wave_sum(sum);
+    zt = wave_sum(zt);
+    if (lane == 0) ce_rows[row] = mx + __logf(sum) - zt;
+  }
+}
+
+// out[d] = (KL, RL[, CE]).  lda: RL is the mean of rl_rows in draw order (as
+// gfk_score_mean_k takes it), else the ProdLDA launch's own, from the workspace.
+__global__ void __launch_bounds__(SC_THREADS) gfk_score_finish_k(GfkScoreX x, int lda) {
+  const int d = blockIdx.x * SC_THREADS + threadIdx.x;
+  if (d >= x.s.n_docs) return;
+  const int R = x.s.n_samples > 0 ? x.s.n_samples : 1;
+  float* o = x.out + (size_t)d * x.ncol;
+  o[0] = x.s.out[2 * (size_t)d];
+  if (lda) {
+    float t = 0.f;
+    for (int s = 0; s < R; ++s) t += x.s.rl_rows[(size_t)d * R + s];
+    o[1] = t / (float)R;
+  } else {
+    o[1] = x.s.out[2 * (size_t)d + 1];
+  }
+  if (x.ncol == 3) {
+    float t = 0.f;
+    for (int s = 0; s < R; ++s) t += x.ce_rows[(size_t)d * R + s];
+    o[2] = t / (float)R;
+  }
+}
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+extern "C" size_t gfk_scorex_struct_size() { return sizeof(GfkScoreX); }
+
+// L[k] of the eval-mode NeuralLDA decoder into lse [K]; part: workspace
+// [gfk_score_vranges(V), K, 2].  Depends on the model alone: once per score call.
+extern "C" int gfk_lda_topic_lse(const GfkModel* m, float* part, float* lse, int max_grid, hipStream_t s) {
+  if (m->K <= 0 || m->K > LS_KMAX || m->V <= 0 || m->ldb < m->V || max_grid < 0) return -5;
+  if (!part || !lse) return -7;
+  if (!m->beta || !m->beta_rm || !m->beta_rv) return -8;
+  TopicLseArgs a;
+  a.beta = m->beta; a.rm = m->beta_rm; a.rv = m->beta_rv;
+  a.part = part; a.lse = lse;
+  a.V = m->V; a.K = m->K; a.ldb = m->ldb; a.bn_eps = m->bn_eps;
+  a.vec = (m->ldb % TL_VEC == 0) && aligned16(m->beta) && aligned16(m->beta_rm) && aligned16(m->beta_rv);
+  int grid = m->K * sc_vranges(m->V);
+  if (max_grid > 0 && grid > max_grid) grid = max_grid;
+  hipLaunchKernelGGL(gfk_lda_topic_lse_k, dim3(grid), dim3(SC_THREADS), 0, s, a);
+  int rc = (int)hipGetLastError();
+  if (rc) return rc;
+  hipLaunchKernelGGL(gfk_lda_topic_lse_fin_k, dim3((m->K + SC_THREADS - 1) / SC_THREADS), dim3(SC_THREADS),
+                     0, s, a);
+  return (int)hipGetLastError();
+}
+
+// (KL, RL[, CE]) of a chunk on either decoder.  ProdLDA: gfk_doc_score into the workspace
+// x->s.out, then the label head (plain ProdLDA has gfk_doc_score itself).  NeuralLDA: the
+// theta kernel, then the sparse term against x->topic_lse.  Host checks as gfk_doc_score's.
+extern "C" int gfk_score_ext(const GfkModel* m, const GfkScoreX* x, hipStream_t s) {
+  const GfkScore* p = &x->s;
+  if (p->n_docs <= 0) return 0;
+  const bool lda = m->kind != GFK_PRODLDA;
+  const bool ce = x->labels != nullptr;
+  if (m->K <= 0 || m->K > LS_KMAX || m->V <= 0 || m->ldb < m->V || p->grid <= 0 || p->n_samples < 0 ||
+      p->max_grid < 0 || x->ncol != (ce ? 3 : 2) || (ce && (m->L <= 0 || m->L > 256)))
+    return -5;
+  if (!lda && !ce) return -2;                // plain ProdLDA: gfk_doc_score
+  const int64_t R = p->n_samples > 0 ? p->n_samples : 1;
+  if (R * p->n_docs >= ((int64_t)1 << 31)) return -6;
+  if (!p->indptr || !p->indices || !p->values || !p->moments || !p->theta || !p->rl_rows || !p->out ||
+      !x->out || (lda && !x->topic_lse) || (!lda && !p->lse_part) || (ce && !x->ce_rows))
+    return -7;
+  if (!m->beta || !m->beta_rm || !m->beta_rv || !m->prior_mean || !m->prior_var ||
+      (ce && (!m->w_cls || !m->b_cls)))
+    return -8;
+  ScoreArgs a;
+  a.beta = m->beta; a.beta_rm = m->beta_rm; a.beta_rv = m->beta_rv;
+  a.prior_mean = m->prior_mean; a.prior_var = m->prior_var;
+  a.V = m->V; a.K = m->K; a.ldb = m->ldb; a.bn_eps = m->bn_eps;
+  const int64_t cap = p->max_grid > 0 ? p->max_grid : ((int64_t)1 << 31);
+  auto capped = [&](int64_t g) { return (unsigned)(g < cap ? g : cap); };
+  const int64_t wdocs = (p->n_docs + SC_WAVES - 1) / SC_WAVES;
+  const int64_t wrows = (R * p->n_docs + SC_WAVES - 1) / SC_WAVES;
+  int rc;
+  if (lda) {
+    hipLaunchKernelGGL(gfk_score_theta_k, dim3(capped(wdocs < 2048 ? wdocs : 2048)), dim3(SC_THREADS), 0, s,
+                       a, *p);
+    rc = (int)hipGetLastError();
+    if (rc) return rc;
+    const dim3 g(capped(wdocs < 8192 ? wdocs : 8192));
+    if (R == 1) hipLaunchKernelGGL(gfk_lda_sparse_k<1>, g, dim3(SC_THREADS), 0, s, a, *p, x->topic_lse);
+    else hipLaunchKernelGGL(gfk_lda_sparse_k<4>, g, dim3(SC_THREADS), 0, s, a, *p, x->topic_lse);
+    rc = (int)hipGetLastError();
+  } else {
+    rc = gfk_doc_score(m, p, s);
+  }
+  if (rc) return rc;
+  if (ce) {
+    hipLaunchKernelGGL(gfk_label_ce_k, dim3(capped(wrows < 8192 ? wrows : 8192)), dim3(SC_THREADS), 0, s, a,
+                       *p, x->labels, (const float*)m->w_cls, (const float*)m->b_cls, x->ce_rows, (int)m->L);
+    rc = (int)hipGetLastError();
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(gfk_score_finish_k, dim3((p->n_docs + SC_THREADS - 1) / SC_THREADS), dim3(SC_THREADS), 0,
+                     s, *x, lda ? 1 : 0);
   return (int)hipGetLastError();
 }

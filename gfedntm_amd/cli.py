@@ -80,6 +80,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="local/rccl/gloo: after training, the NPMI coherence of the global model's "
                         "top-N words over every client's documents (integer co-occurrence counts "
                         "are summed; the documents stay with their client); 0 = off")
+    p.add_argument("--perplexity_completion", type=float, default=0.0, metavar="RHO",
+                   help="local/rccl/gloo: after training, the document-completion perplexity of the "
+                        "global model over every client's documents (each client observes a token "
+                        "with probability RHO and is scored on the rest; four sums per client are "
+                        "added, the documents stay with their client); 0 = off")
     p.add_argument("--collective_timeout", type=float, default=1800.0,
                    help="rccl/gloo: process-group timeout in seconds (failed collectives abort)")
     p.add_argument("--heartbeat_timeout", type=float, default=120.0,
@@ -163,6 +168,12 @@ def run_local(args, cfg) -> dict:
         coh = fed.coherence(topk=args.npmi_topk)
         log_coherence(logger, coh, args.npmi_topk)
         out.update(npmi=coh["npmi"], npmi_topk=args.npmi_topk, topic_diversity=coh["diversity"])
+    if args.perplexity_completion > 0:
+        from .federation.runner import log_perplexity
+        ppl = fed.perplexity(completion=args.perplexity_completion, seed=args.seed)
+        log_perplexity(logger, ppl)
+        out.update(perplexity=ppl["perplexity"], perplexity_completion=ppl["completion"],
+                   perplexity_tokens=ppl["tokens_heldout"], perplexity_engine=ppl["engine"])
     return out
 
 
@@ -201,7 +212,7 @@ def _rank_main(args, cfg) -> dict:
         metrics_path=os.path.join(f"{logs_client}{ids[0]}", f"metrics_{stamp}.jsonl"),
         metrics_every=args.metrics_every, heartbeat_timeout=args.heartbeat_timeout,
         agg_mode=args.agg, client_ids=ids, fedavg_wire=args.fedavg_wire or cfg.fedavg_wire,
-        coherence_topk=args.npmi_topk)
+        coherence_topk=args.npmi_topk, perplexity_completion=args.perplexity_completion)
 
 
 def _spawned(local_rank: int, world: int, port: int, argv: List[str]):
@@ -248,6 +259,11 @@ def main(argv: Optional[List[str]] = None):
     if args.npmi_topk > 0 and args.backend == "grpc":
         raise SystemExit("--npmi_topk needs a collective backend (local / rccl / gloo): the "
                          "reference wire protocol has no message for co-occurrence counts")
+    if not 0.0 <= args.perplexity_completion < 1.0:
+        parser.error("--perplexity_completion must lie in [0, 1)")
+    if args.perplexity_completion > 0 and args.backend == "grpc":
+        raise SystemExit("--perplexity_completion needs a collective backend (local / rccl / gloo): "
+                         "the reference wire protocol has no message for the clients' sums")
     from .utils.config import load_config
     cfg = load_config(args.config)
     if args.matmul_dtype is not None:

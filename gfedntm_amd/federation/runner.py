@@ -135,6 +135,71 @@ def log_coherence(logger, coh: Dict, topk: int):
                 float(np.mean(coh["per_topic"])), coh["diversity"], coh["n_docs"], coh["clients"])
 
 
+def federation_perplexity(tm, datas, completion: float = 0.5, n_samples: int = 1, seed: int = 0,
+                          client_ids: Optional[Sequence[int]] = None, group=False,
+                          engine: Optional[str] = None) -> Dict:
+    """Document-completion perplexity of ``tm`` over document shards ``datas`` that stay
+    where they are (and, with a process group, over every rank's).  Client c -- its position
+    in ``datas``, or ``client_ids[j]`` -- splits its own shard (``ops/thin.py split(data,
+    completion, seed + c)``: document indices are local), the encoder reads the observed
+    part and the reconstruction term is taken on the held-out rest with draw seed
+    ``seed + c``.  A client contributes four numbers: the sum of its documents' fp32 RL rows
+    taken in float64 in document order, its held-out and observed token counts and its
+    document count.  With a group the clients' tuples are all-gathered and summed in client
+    order on every rank, so the value is identical everywhere.  ``engine``: None = the fused
+    scorer wherever ``ops.engine.score_covers`` holds, else the PyTorch path; "fused" /
+    "torch" force one.  Returns ``perplexity`` = exp(sum RL / sum held-out tokens),
+    ``rl_sum``, ``tokens_heldout``, ``tokens_observed``, ``n_docs``, ``clients``,
+    ``completion`` and ``engine``."""
+    from ..ops import thin
+    from ..ops.engine import score_covers
+    completion = float(completion)
+    if not 0.0 < completion < 1.0:
+        raise ValueError("completion must lie strictly between 0 and 1")
+    if engine not in (None, "fused", "torch"):
+        raise ValueError("engine must be None, 'fused' or 'torch'")
+    datas = list(datas)
+    ids = list(range(len(datas))) if client_ids is None else [int(c) for c in client_ids]
+    if len(ids) != len(datas):
+        raise ValueError("one client id per shard")
+    if engine is None:
+        engine = "fused" if score_covers(tm) else "torch"
+    elif engine == "fused":
+        score_covers(tm, explain=True)
+    parts = []
+    for c, data in zip(ids, datas):
+        obs, held = thin.split(data, completion, seed + c)
+        if engine == "fused":
+            rl = tm.engine.score(obs, n_samples, seed=seed + c, target=held)[:, 1]
+        else:
+            rl = tm._score_torch(obs, n_samples, seed + c, None, target=held)[1]
+        rl64 = np.asarray(rl.detach().cpu().numpy(), dtype=np.float32).astype(np.float64)
+        rl_sum = 0.0
+        for v in rl64:          # document order (np.sum would add pairwise)
+            rl_sum += float(v)
+        parts.append((c, rl_sum, int(held.values.sum(dtype=torch.float64).item()),
+                      int(obs.values.sum(dtype=torch.float64).item()), int(data.n_docs)))
+    import torch.distributed as dist
+    if group is not False and (group is not None or (dist.is_available() and dist.is_initialized())):
+        gathered: List = [None] * dist.get_world_size(group)
+        dist.all_gather_object(gathered, parts, group=group)
+        parts = [p for g in gathered for p in g]
+    parts.sort(key=lambda p: p[0])
+    rl_sum = 0.0
+    for p in parts:
+        rl_sum += p[1]
+    held, obs, n_docs = (sum(p[i] for p in parts) for i in (2, 3, 4))
+    return {"perplexity": float(np.exp(rl_sum / held)) if held > 0 else float("nan"),
+            "rl_sum": rl_sum, "tokens_heldout": held, "tokens_observed": obs, "n_docs": n_docs,
+            "clients": len(parts), "completion": completion, "engine": engine}
+
+
+def log_perplexity(logger, ppl: Dict):
+    logger.info("-- -- Global completion perplexity@%.2f: %.4f (%d held-out tokens, %d documents, "
+                "%d clients, %s scorer)", ppl["completion"], ppl["perplexity"], ppl["tokens_heldout"],
+                ppl["n_docs"], ppl["clients"], ppl["engine"])
+
+
 # ---- runs of rounds per graph replay: where a run ends (pure functions of the plans) ----
 def round_cuts(epoch_ends, heavy, last: int, warmup_end: Optional[int] = None,
                device_sums: bool = False) -> set:
@@ -501,6 +566,17 @@ class LocalFederation:
         return federation_coherence(self.clients[0].tm, [c.data for c in self.clients], topk,
                                     matrix, per_topic, group=False, n_clients=len(self.clients))
 
+    def perplexity(self, completion: float = 0.5, n_samples: int = 1, seed: int = 0,
+                   engine: Optional[str] = None) -> Dict:
+        """Document-completion perplexity of the global model (``clients[0].tm``, as in
+        :meth:`coherence`) on the union of the clients' documents, which stay in their
+        shards: :func:`federation_perplexity` with the clients' ids, so a collective run of
+        the same federation (``run_distributed(perplexity_completion=)``) splits and draws
+        alike."""
+        return federation_perplexity(self.clients[0].tm, [c.data for c in self.clients], completion,
+                                     n_samples, seed, client_ids=[c.id for c in self.clients],
+                                     group=False, engine=engine)
+
     def save_global(self, path: str):
         """The global model = the averaged state (B4/B5); betas only, like the reference."""
         tm = self.clients[0].tm
@@ -536,7 +612,7 @@ def run_distributed(corpus, params: Dict, model_type: str = "avitm",
                     rehearse_1gpu: Optional[bool] = None, allreduce: Optional[str] = None,
                     round_hook=None, client_ids: Optional[Sequence[int]] = None,
                     keep_round: bool = False, fedavg_wire: str = "fp32",
-                    coherence_topk: int = 0) -> Dict:
+                    coherence_topk: int = 0, perplexity_completion: float = 0.0) -> Dict:
     """Runs this process's client(s); torch.distributed must be initialised (RANK /
     WORLD_SIZE).  ``corpus`` is this rank's one client (id rank + 1), or a list of client
     corpora with their ids ``client_ids`` -- a contiguous block of a federation of more
@@ -590,7 +666,13 @@ def run_distributed(corpus, params: Dict, model_type: str = "avitm",
     co-occurrences of the global model's top words on its clients' shards, the ranks
     all-reduce the integer counts once over the control plane, and the result gains
     ``npmi``, ``npmi_topk`` and ``topic_diversity`` (identical on every rank; the documents
-    stay where they are).  0: no extra collective, no extra keys."""
+    stay where they are).  0: no extra collective, no extra keys.
+
+    ``perplexity_completion`` = rho in (0, 1): after the last round every rank scores its
+    clients' shards by document completion (:func:`federation_perplexity`, draw and split
+    seeds ``seed`` + client id), the clients' four sums are all-gathered once over the control
+    plane, and the result gains ``perplexity``, ``perplexity_completion``,
+    ``perplexity_tokens`` and ``perplexity_engine`` (identical on every rank).  0: off."""
     import torch.distributed as dist
     from .hierarchical import agree_client_map
     from .rank_round import MultiClientRound, SingleClientRound
@@ -688,6 +770,14 @@ def run_distributed(corpus, params: Dict, model_type: str = "avitm",
                 log_coherence(logger, coh, coherence_topk)
             out.update(npmi=coh["npmi"], npmi_topk=int(coherence_topk),
                        topic_diversity=coh["diversity"])
+        if perplexity_completion > 0:
+            ppl = federation_perplexity(clients[0].tm, [c.data for c in clients],
+                                        perplexity_completion, seed=seed, client_ids=client_ids,
+                                        group=ctrl)
+            if rank == 0:
+                log_perplexity(logger, ppl)
+            out.update(perplexity=ppl["perplexity"], perplexity_completion=ppl["completion"],
+                       perplexity_tokens=ppl["tokens_heldout"], perplexity_engine=ppl["engine"])
         ok = True
         return out
     finally:

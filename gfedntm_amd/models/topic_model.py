@@ -359,7 +359,9 @@ class TopicModelBase:
         label head; ``perplexity``: exp(sum(KL + RL) / tokens); ``engine``: "fused"
         (csrc/score.hip) or "torch" (the eval-mode modules; ``engine_info`` says why).
         ``eps``: explicit normals [n_samples, D, K] -- PyTorch engine only; ``engine``
-        forces one of the two ("fused" raises where the kernels do not cover the model).
+        forces one of the two ("fused" raises where the kernels do not cover the model:
+        ``ops.engine.score_covers``, which also takes the NeuralLDA decoder and label heads
+        that the default, ``score_supports``, still leaves to the PyTorch engine).
 
         ``completion=rho`` (0 < rho < 1) scores by document completion: every token is
         observed with probability rho (``ops/thin.py split``, keyed by ``split_seed`` --
@@ -383,14 +385,15 @@ class TopicModelBase:
         if engine == "fused":
             if eps is not None:
                 raise ValueError("explicit eps runs on the PyTorch engine only")
-            from ..ops.engine import score_supports
-            score_supports(self, explain=True)
+            from ..ops.engine import score_covers
+            score_covers(self, explain=True)
         elif engine is None:
             engine = "torch" if eps is not None else self._score_engine()[0]
         ce = None
         if engine == "fused":
             klrl = self.engine.score(data, n_samples, seed=seed, target=target).cpu().numpy()
             kl, rl = klrl[:, 0].copy(), klrl[:, 1].copy()
+            ce = klrl[:, 2].copy() if klrl.shape[1] == 3 else None
         else:
             kl, rl, ce = self._score_torch(data, n_samples, seed, eps, target=target)
             packed = torch.stack([kl, rl] + ([ce] if ce is not None else []), 1).cpu().numpy()
@@ -419,11 +422,12 @@ class TopicModelBase:
         return out
 
     def perplexity(self, dataset, n_samples: int = 1, seed: Optional[int] = None,
-                   completion: Optional[float] = None, split_seed: Optional[int] = None) -> float:
+                   completion: Optional[float] = None, split_seed: Optional[int] = None,
+                   engine: Optional[str] = None) -> float:
         """exp(sum_d (KL_d + RL_d) / sum_d N_d) -- shorthand for :meth:`score`; with
         ``completion``, the predictive exp(sum_d RL_d / held-out tokens)."""
         return self.score(dataset, n_samples=n_samples, seed=seed, completion=completion,
-                          split_seed=split_seed)["perplexity"]
+                          split_seed=split_seed, engine=engine)["perplexity"]
 
     def fit(self, train_dataset, validation_dataset=None, save_dir=None, patience=5, delta=0,
             n_samples=20):

@@ -242,6 +242,31 @@ def score_supports(tm, explain: bool = False) -> bool:
     return True
 
 
+SCORE_EXT_MAX_K = 256      # csrc/score.hip LS_KMAX: the NeuralLDA and label-head kernels
+
+
+def score_covers(tm, explain: bool = False) -> bool:
+    """What the fused scorer (csrc/score.hip) can run -- wider than what runs on it by default
+    (:func:`score_supports`): a fused backend, the ProdLDA or the NeuralLDA decoder, with or
+    without a label head; NeuralLDA and label-head models within the K of their kernels.
+    ``TopicModelBase.score(engine="fused")`` and ``FusedEngine.score`` accept exactly this."""
+    lda = tm.model_type.lower() != "prodlda"
+    head = bool(getattr(tm, "label_size", 0))
+    checks = [
+        (getattr(tm, "backend", None) == "fused", "the model runs on the PyTorch engine"),
+        (tm.n_components <= 512, "n_components > 512"),
+        (not (lda or head) or tm.n_components <= SCORE_EXT_MAX_K,
+         f"n_components > {SCORE_EXT_MAX_K} with the NeuralLDA decoder or a label head"),
+        (int(getattr(tm, "label_size", 0) or 0) <= 256, "label_size > 256"),
+    ]
+    for ok, why in checks:
+        if not ok:
+            if explain:
+                raise RuntimeError(f"fused scoring unsupported: {why}")
+            return False
+    return True
+
+
 UPDATE_GRAD, UPDATE_FUSED = 0, 1
 
 
@@ -1493,24 +1518,36 @@ class FusedEngine(EngineBase):
     def score(self, data: DeviceCSR, n_samples: int = 1, seed: int = 0,
               chunk: Optional[int] = None, target: Optional[DeviceCSR] = None,
               max_grid: Optional[int] = None) -> torch.Tensor:
-        """Held-out ELBO terms [D, 2] = (KL, RL) of every document of ``data``
-        (csrc/score.hip): the eval-mode encoder once per document (gfk_theta_infer, the
-        posterior moments), then the eval-mode ProdLDA decoder over ``n_samples`` draws of
-        theta = softmax(mu + eps * sigma) per document -- the normals of ``theta_infer``
-        for the same seed; ``n_samples=0`` scores the plug-in theta = softmax(mu).  RL is
-        the mean over the draws, KL is exact.  Always fp32.  No dense [rows, V] matrix is
-        built and nothing is read back: the result stays on the device.  Draws are keyed by
-        (seed, document index), so neither the chunking nor the grid changes the result.
+        """Held-out ELBO terms [D, 2] = (KL, RL) of every document of ``data`` -- [D, 3] =
+        (KL, RL, CE) for a label-head model -- (csrc/score.hip): the eval-mode encoder once
+        per document (gfk_theta_infer, the posterior moments), then the eval-mode decoder
+        over ``n_samples`` draws of theta = softmax(mu + eps * sigma) per document -- the
+        normals of ``theta_infer`` for the same seed; ``n_samples=0`` scores the plug-in
+        theta = softmax(mu).  RL (and CE) is the mean over the draws, KL is exact.  Always
+        fp32.  No dense [rows, V] matrix is built and nothing is read back: the result stays
+        on the device.  Draws are keyed by (seed, document index), so neither the chunking
+        nor the grid changes the result.
+
+        ProdLDA: the MFMA log-sum-exp over the vocabulary plus the sparse term.  NeuralLDA:
+        theta @ softmax(BN(beta)) is never renormalised over V, so only the non-zeros are
+        touched, against a per-topic log-sum-exp computed once per call (no normalised [K, V]
+        matrix either).  A label head adds the classifier cross-entropy against
+        argmax(``data.labels``) and needs those labels (``ValueError`` without).
+
         ``target``: a second CSR of the same documents (document completion, ops/thin.py
         split): the encoder reads ``data``, the sparse reconstruction term ``target``.
         ``max_grid`` caps the workgroups of every strided launch, the encoder's included (as in
         ``theta_infer``); the result does not depend on it."""
-        score_supports(self.tm, explain=True)
+        score_covers(self.tm, explain=True)
         m, K, n, S = self._m, int(self._m.K), int(data.n_docs), int(n_samples)
         if S < 0:
             raise ValueError("n_samples must be >= 0")
         R = max(S, 1)
-        out = torch.empty(n, 2, dtype=torch.float32, device=self.device)
+        lda, head = m.kind != abi.KIND_PRODLDA, bool(m.lab_on)
+        if head and data.labels is None:
+            raise ValueError("this model encodes labels: inference data needs them")
+        ncol = 3 if head else 2
+        out = torch.empty(n, ncol, dtype=torch.float32, device=self.device)
         if not n:
             return out
         if chunk is None:       # <= 64 Ki rows of theta per launch
@@ -1529,27 +1566,56 @@ class FusedEngine(EngineBase):
         theta = torch.empty(rows, K, **f)
         rl_rows = torch.empty(rows, **f)
         nv = int(self.lib.gfk_score_vranges(C.byref(m)))    # vocabulary ranges per row block
-        lse_part = torch.empty(nv * rows * 2, **f)
+        lse_part = None if lda else torch.empty(nv * rows * 2, **f)
         cu = torch.cuda.get_device_properties(self.device).multi_processor_count
         stream = torch.cuda.current_stream(self.device).cuda_stream
         block = 64 if K <= 256 else 32                  # rows per workgroup (csrc/score.hip)
         wg_per_cu = max(1, min(4, LDS_LIMIT // max(int(self.lib.gfk_doc_score_smem(C.byref(m))), 1)))
+        cap = 0 if max_grid is None else _max_grid(max_grid)
+        ext = lda or head
+        if ext:
+            klrl = torch.empty(min(n, chunk), 2, **f)   # the launches' (KL, ProdLDA RL) workspace
+            ce_rows = torch.empty(rows, **f) if head else None
+            labels = data.labels.contiguous() if head else None
+            if head and (labels.dtype != torch.float32 or tuple(labels.shape) != (n, int(m.L))):
+                raise ValueError(f"labels must be float32 [{n}, {int(m.L)}]")
+        topic_lse = None
+        if lda:                 # the decoder's per-topic log-sum-exp: the model's alone, once
+            topic_lse = torch.empty(K, **f)
+            part = torch.empty(nv * K * 2, **f)
+            rc = self.lib.gfk_lda_topic_lse(C.byref(m), part.data_ptr(), topic_lse.data_ptr(), cap, stream)
+            if rc:
+                raise RuntimeError(f"gfk_lda_topic_lse failed ({rc})")
         for d0 in range(0, n, chunk):
             d1 = min(n, d0 + chunk)
             self._infer_launch(data, d0, d1, mom.data_ptr(), 1, abi.INFER_MOMENTS, 0.0, seed,
                                max_grid)
-            p = abi.GfkScore()
+            x = abi.GfkScoreX()
+            p = x.s if ext else abi.GfkScore()
             p.indptr = rec.indptr.data_ptr() + 4 * d0
             p.indices, p.values = rec.indices.data_ptr(), rec.values.data_ptr()
-            p.moments, p.theta, p.lse_part = mom.data_ptr(), theta.data_ptr(), lse_part.data_ptr()
-            p.rl_rows, p.out = rl_rows.data_ptr(), out.data_ptr() + 8 * d0
+            p.moments, p.theta = mom.data_ptr(), theta.data_ptr()
+            p.lse_part = lse_part.data_ptr() if lse_part is not None else None
+            p.rl_rows = rl_rows.data_ptr()
             p.n_docs, p.n_samples = d1 - d0, S
             p.seed, p.doc0 = int(seed) % (1 << 64), d0
             p.grid = int(max(1, min(-(-(d1 - d0) * R // block) * nv, wg_per_cu * cu)))
-            p.max_grid = 0 if max_grid is None else _max_grid(max_grid)
-            rc = self.lib.gfk_doc_score(C.byref(m), C.byref(p), stream)
+            p.max_grid = cap
+            if not ext:
+                p.out = out.data_ptr() + 8 * d0
+                rc = self.lib.gfk_doc_score(C.byref(m), C.byref(p), stream)
+                if rc:
+                    raise RuntimeError(f"gfk_doc_score failed ({rc})")
+                continue
+            p.out = klrl.data_ptr()
+            x.out, x.ncol = out.data_ptr() + 4 * ncol * d0, ncol
+            x.topic_lse = topic_lse.data_ptr() if lda else None
+            if head:
+                x.labels = labels.data_ptr() + 4 * int(m.L) * d0
+                x.ce_rows = ce_rows.data_ptr()
+            rc = self.lib.gfk_score_ext(C.byref(m), C.byref(x), stream)
             if rc:
-                raise RuntimeError(f"gfk_doc_score failed ({rc})")
+                raise RuntimeError(f"gfk_score_ext failed ({rc})")
         return out
 
     # ------------------------------------------------------------------ step

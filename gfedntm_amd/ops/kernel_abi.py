@@ -189,6 +189,13 @@ class GfkScore(C.Structure):
                 ("grid", C.c_int32), ("doc0", C.c_int32), ("max_grid", C.c_int32)]
 
 
+class GfkScoreX(C.Structure):
+    """held-out scoring launch on the NeuralLDA decoder and / or with a label head
+    (csrc/score.hip gfk_score_ext): ``s.out`` is a [n_docs, 2] workspace there."""
+    _fields_ = [("s", GfkScore), ("labels", P), ("topic_lse", P), ("ce_rows", P), ("out", P),
+                ("ncol", C.c_int32), ("reserved", C.c_int32)]
+
+
 class GfkCooc(C.Structure):
     """word co-occurrence counting launch (csrc/cooc.hip)."""
     _fields_ = [("indptr", P), ("indices", P), ("values", P), ("slot", P), ("bits", P),
@@ -269,6 +276,13 @@ def declare(lib: C.CDLL) -> None:
     lib.gfk_doc_score_smem.restype = C.c_size_t
     lib.gfk_score_vranges.argtypes = [C.POINTER(GfkModel)]
     lib.gfk_score_vranges.restype = C.c_int
+    lib.gfk_scorex_struct_size.restype = C.c_size_t
+    if lib.gfk_scorex_struct_size() != C.sizeof(GfkScoreX):
+        raise RuntimeError("GfkScoreX ABI mismatch")
+    lib.gfk_score_ext.argtypes = [C.POINTER(GfkModel), C.POINTER(GfkScoreX), C.c_void_p]
+    lib.gfk_score_ext.restype = C.c_int
+    lib.gfk_lda_topic_lse.argtypes = [C.POINTER(GfkModel), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.gfk_lda_topic_lse.restype = C.c_int
     lib.gfk_cooc_struct_size.restype = C.c_size_t
     if lib.gfk_cooc_struct_size() != C.sizeof(GfkCooc):
         raise RuntimeError("GfkCooc ABI mismatch")

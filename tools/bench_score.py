@@ -4,8 +4,12 @@ PyTorch path of the same model (``engine="torch"``: the eval-mode modules over d
 [chunk, V] rows), same GPU, one draw per document (the validation estimator), interleaved.
 
 The two shapes are the README's ProdLDA ones: K = 50 V = 4466 and K = 200 V = 112k.
+``--model LDA`` times the NeuralLDA decoder on the same shapes (``engine="fused"`` there is
+the sparse-only scorer: a per-topic log-sum-exp once per call and the non-zeros; the default
+engine of such a model is still the PyTorch path).
 
-usage: python tools/bench_score.py [--shape small|large|both] [--reps 7] [--out FILE]
+usage: python tools/bench_score.py [--shape small|large|both] [--model prodLDA|LDA] [--reps 7]
+                                   [--out FILE]
 Prints one JSON line per shape (docs/s of each path: the median of --reps windows, and the
 spread), appended to --out when given.
 """
@@ -45,14 +49,14 @@ def window(fn, min_s=0.25):
     return t / n
 
 
-def run(name, cfg, reps, steps):
+def run(name, cfg, reps, steps, model_type="prodLDA"):
     dev = torch.device("cuda")
     K, V = cfg["K"], cfg["V"]
     corpus = generate_synthetic(vocab_size=V, n_topics=K, n_docs=cfg["base"], n_nodes=1,
                                 frozen_topics=5, seed=0)
     X = remap_to_vocabulary(corpus, 0, {f"wd{i}": i for i in range(V)})
     X = sp.vstack([X] * (-(-cfg["docs"] // cfg["base"]))).tocsr()[: cfg["docs"]]
-    tm = AVITM(input_size=V, n_components=K, hidden_sizes=cfg["hidden"], batch_size=64,
+    tm = AVITM(input_size=V, n_components=K, model_type=model_type, hidden_sizes=cfg["hidden"], batch_size=64,
                verbose=False, device=dev, backend="fused", seed=0)
     ds = BOWDataset(X, None)
     data = tm.device_data(ds)
@@ -72,7 +76,8 @@ def run(name, cfg, reps, steps):
             times[k].append(window(f))
     n = data.n_docs
     med = {k: statistics.median(v) for k, v in times.items()}
-    out = {"metric": "held-out scoring docs/s (1 draw per document)", "shape": name, "K": K, "V": V,
+    out = {"metric": "held-out scoring docs/s (1 draw per document)", "shape": name, "model": model_type,
+           "K": K, "V": V,
            "docs": n, "nnz": int(data.nnz), "reps": reps,
            "fused_docs_per_s": round(n / med["fused"], 1), "fused_ms": round(med["fused"] * 1e3, 3),
            "fused_ms_min_max": [round(min(times["fused"]) * 1e3, 3), round(max(times["fused"]) * 1e3, 3)],
@@ -90,6 +95,7 @@ def run(name, cfg, reps, steps):
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--shape", default="both", choices=["small", "large", "both"])
+    p.add_argument("--model", default="prodLDA", choices=["prodLDA", "LDA"])
     p.add_argument("--reps", type=int, default=7)
     p.add_argument("--steps", type=int, default=20, help="training steps before scoring")
     p.add_argument("--out", default=None, help="append the JSON lines to this file")
@@ -97,7 +103,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench_score needs a GPU")
     for name in (["small", "large"] if a.shape == "both" else [a.shape]):
-        line = json.dumps(run(name, SHAPES[name], a.reps, a.steps))
+        line = json.dumps(run(name, SHAPES[name], a.reps, a.steps, a.model))
         print(line, flush=True)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
