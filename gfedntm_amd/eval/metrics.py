@@ -16,7 +16,9 @@
   (csrc/cooc.hip) or a host CSR, per client -- and summed: ``cooccurrence_counts``,
   ``federated_cooccurrence``, ``npmi_from_counts`` (the same float64 formula).
 * Topic diversity (TD) and rank-biased overlap (RBO) -- tm_wrapper.py:386-400.
-* Word-mover's distance between topic sets given word vectors -- aux_scripts/evaluation/wmd.py.
+* Word-mover's distance between topic sets given word vectors -- aux_scripts/evaluation/wmd.py:
+  one LP per topic pair by default; ``engine="host"`` / ``"device"`` solve the whole
+  [K_ref, K_cmp] batch with the exact transport solver of ops/wmd.py (csrc/wmd.hip).
 """
 from __future__ import annotations
 
@@ -337,9 +339,55 @@ def inverted_rbo(topics: Sequence[Sequence], topk: int = 10, p: float = 0.9) -> 
     return float(1.0 - np.mean(vals))
 
 
-def word_movers_distance(words1: Sequence[str], words2: Sequence[str], vectors: Dict[str, np.ndarray]
-                         ) -> float:
-    """WMD between two bags of words with uniform weights (exact EMD via LP)."""
+_WMD_ENGINES = (None, "lp", "host", "device")
+
+
+class WordTable:
+    """Word vectors as one [W, dim] float64 table plus ``index`` (word -> row), for the batched
+    WMD engines: built once (``device=True``: uploaded once) and shared by every
+    :func:`mean_min_wmd` call that compares topics over these words.  Reads like the dict it
+    was built from (``word in table``, ``table[word]``)."""
+
+    def __init__(self, vectors: Dict[str, np.ndarray], words=None, device: bool = False):
+        keep = list(vectors) if words is None else [w for w in dict.fromkeys(words) if w in vectors]
+        self.index = {w: i for i, w in enumerate(keep)}
+        self.host = (np.stack([np.asarray(vectors[w], dtype=np.float64) for w in keep])
+                     if keep else np.zeros((0, 0)))
+        self.table = self.host
+        if device:
+            import torch
+            self.table = torch.from_numpy(self.host).cuda()
+
+    def __contains__(self, word) -> bool:
+        return word in self.index
+
+    def __getitem__(self, word) -> np.ndarray:
+        return self.host[self.index[word]]
+
+
+def _wmd_batched(lists1, lists2, vectors, engine) -> np.ndarray:
+    """[len(lists1), len(lists2)] WMDs of word lists on the "host" / "device" engine
+    (ops/wmd.py); words without a vector are dropped, a list left empty gives inf."""
+    from ..ops import wmd
+    if not isinstance(vectors, WordTable):
+        vectors = WordTable(vectors, (w for l in list(lists1) + list(lists2) for w in l))
+    ix = vectors.index
+    la = [[ix[w] for w in l if w in ix] for l in lists1]
+    lb = [[ix[w] for w in l if w in ix] for l in lists2]
+    if not ix:
+        return np.full((len(la), len(lb)), np.inf)
+    return wmd.pairwise_wmd(la, lb, vectors.table, engine=engine)
+
+
+def word_movers_distance(words1: Sequence[str], words2: Sequence[str], vectors: Dict[str, np.ndarray],
+                         engine: Optional[str] = None) -> float:
+    """WMD between two bags of words with uniform weights.  ``engine``: None / "lp" -- exact EMD
+    via one LP (scipy HiGHS); "host" / "device" -- the exact transport solver of ops/wmd.py
+    (numpy twin / csrc/wmd.hip kernels)."""
+    if engine not in _WMD_ENGINES:
+        raise ValueError("engine must be None, 'lp', 'host' or 'device'")
+    if engine in ("host", "device"):
+        return float(_wmd_batched([list(words1)], [list(words2)], vectors, engine)[0, 0])
     from scipy.optimize import linprog
     a = [w for w in words1 if w in vectors]
     b = [w for w in words2 if w in vectors]
@@ -360,8 +408,17 @@ def word_movers_distance(words1: Sequence[str], words2: Sequence[str], vectors: 
 
 
 def mean_min_wmd(topics_ref: List[List[str]], topics_cmp: List[List[str]],
-                 vectors: Dict[str, np.ndarray], n_words: int = 10) -> float:
-    """Mean over reference topics of the minimum WMD to any compared topic (wmd.py:56-80)."""
-    d = np.array([[word_movers_distance(t1[:n_words], t2[:n_words], vectors) for t2 in topics_cmp]
-                  for t1 in topics_ref])
+                 vectors: Dict[str, np.ndarray], n_words: int = 10,
+                 engine: Optional[str] = None) -> float:
+    """Mean over reference topics of the minimum WMD to any compared topic (wmd.py:56-80).
+    ``engine`` as in :func:`word_movers_distance`; "host" / "device" take the whole
+    [K_ref, K_cmp] matrix in one batched call (``vectors`` may be a :class:`WordTable`)."""
+    if engine not in _WMD_ENGINES:
+        raise ValueError("engine must be None, 'lp', 'host' or 'device'")
+    if engine in ("host", "device"):
+        d = _wmd_batched([t[:n_words] for t in topics_ref], [t[:n_words] for t in topics_cmp],
+                         vectors, engine)
+    else:
+        d = np.array([[word_movers_distance(t1[:n_words], t2[:n_words], vectors) for t2 in topics_cmp]
+                      for t1 in topics_ref])
     return float(np.mean(np.min(d, axis=1)))

@@ -9,17 +9,22 @@ format (``word v1 v2 ...`` per line, optional header) or an ``.npz`` with
 ``words`` and ``vectors`` arrays.  Vectors are L2-normalised like gensim's
 ``init_sims(replace=True)``.  Model folders are the ones written by
 :mod:`gfedntm_amd.experiments.collab` (``topics.json``).
+
+``engine``: None / "lp" -- one LP per topic pair (eval/metrics.py word_movers_distance);
+"host" / "device" -- every cell's [K_ref, K_cmp] problems as one batch of the exact transport
+solver (ops/wmd.py numpy twin / csrc/wmd.hip kernels); with "device" the vectors of a table's
+words are uploaded once per table and every cell gathers from that copy.
 """
 from __future__ import annotations
 
 import argparse
 import json
 import os
-from typing import Dict, List
+from typing import Dict, List, Optional
 
 import numpy as np
 
-from ..eval.metrics import mean_min_wmd
+from ..eval.metrics import WordTable, mean_min_wmd
 
 
 def load_vectors(path: str) -> Dict[str, np.ndarray]:
@@ -46,8 +51,12 @@ def _topics(folder: str) -> List[List[str]]:
 
 
 def wmd_tables(path_models: str, path_save: str, vectors: Dict[str, np.ndarray],
-               nr_tpcs_lst=(10, 20, 30, 40, 50), n_words_lst=(10, 50, 100, 200, 300)):
+               nr_tpcs_lst=(10, 20, 30, 40, 50), n_words_lst=(10, 50, 100, 200, 300),
+               engine: Optional[str] = None):
     import pandas as pd
+    if engine not in (None, "lp", "host", "device"):
+        raise ValueError("engine must be None, 'lp', 'host' or 'device'")
+    batched = engine in ("host", "device")
     names = sorted(n for n in os.listdir(path_models) if os.path.isdir(os.path.join(path_models, n)))
     centr = sorted((n for n in names if n.startswith("centralized")), key=lambda n: int(n.split("_")[1]))
     os.makedirs(path_save, exist_ok=True)
@@ -60,10 +69,16 @@ def wmd_tables(path_models: str, path_save: str, vectors: Dict[str, np.ndarray],
         every = nodes + centr
         for nw in n_words_lst:
             d = np.zeros((len(nodes), len(every)))
+            vec = vectors
+            if batched:                  # one table (one upload) of the words this table compares
+                tops = {name: _topics(os.path.join(path_models, name)) for name in every}
+                vec = WordTable(vectors, (w for ts in tops.values() for t in ts for w in t[:nw]),
+                                device=engine == "device")
             for i, ref in enumerate(nodes):
                 tr = _topics(os.path.join(path_models, ref))
                 for j, cmp_ in enumerate(every):
-                    d[i, j] = mean_min_wmd(tr, _topics(os.path.join(path_models, cmp_)), vectors, nw)
+                    d[i, j] = mean_min_wmd(tr, _topics(os.path.join(path_models, cmp_)), vec, nw,
+                                           engine=engine)
             out = os.path.join(path_save, f"wmds_{k}tpcs_{nw}_words.csv")
             pd.DataFrame(d, index=cols[: len(nodes)], columns=cols).to_csv(out)
             written.append(out)
@@ -77,10 +92,13 @@ def main(argv=None):
     p.add_argument("--vectors", required=True, help="word2vec text file or .npz (words, vectors)")
     p.add_argument("--nr_tpcs_lst", type=str, default="10,20,30,40,50")
     p.add_argument("--n_words_lst", type=str, default="10,50,100,200,300")
+    p.add_argument("--engine", default=None, choices=["lp", "host", "device"],
+                   help="lp (default): one LP per topic pair; host / device: the batched exact "
+                        "transport solver (numpy twin / HIP kernels)")
     a = p.parse_args(argv)
     return wmd_tables(a.path_models, a.path_save, load_vectors(a.vectors),
                       [int(x) for x in a.nr_tpcs_lst.split(",")],
-                      [int(x) for x in a.n_words_lst.split(",")])
+                      [int(x) for x in a.n_words_lst.split(",")], engine=a.engine)
 
 
 if __name__ == "__main__":

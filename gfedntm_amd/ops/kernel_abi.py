@@ -234,6 +234,24 @@ class GfkThin(C.Structure):
 
 THIN_COUNT, THIN_COMPACT = 1, 2
 
+
+class GfkWmdDist(C.Structure):
+    """ground distances between two sets of word vectors (csrc/wmd.hip)."""
+    _fields_ = [("a", P), ("b", P), ("out", P),
+                ("lda", C.c_int64), ("ldb", C.c_int64), ("ldo", C.c_int64),
+                ("Ua", C.c_int32), ("Ub", C.c_int32), ("dim", C.c_int32),
+                ("a_f64", C.c_int32), ("b_f64", C.c_int32), ("max_grid", C.c_int32)]
+
+
+class GfkWmd(C.Structure):
+    """batched uniform-mass optimal transport launch (csrc/wmd.hip)."""
+    _fields_ = [("dist", P), ("a_off", P), ("a_idx", P), ("b_off", P), ("b_idx", P),
+                ("flow", P), ("val", P), ("status", P),
+                ("ldd", C.c_int64), ("flow_len", C.c_int64),
+                ("Ua", C.c_int32), ("Ub", C.c_int32), ("La", C.c_int32), ("Lb", C.c_int32),
+                ("max_a", C.c_int32), ("max_b", C.c_int32), ("cap", C.c_int32),
+                ("max_grid", C.c_int32)]
+
 # optional entry points: name -> (argtypes, restype)
 _EXTRA = {
     "gfk_theta_infer": ([C.POINTER(GfkModel), C.POINTER(GfkInfer), C.c_void_p], C.c_int),
@@ -313,6 +331,22 @@ def declare(lib: C.CDLL) -> None:
     lib.gfk_thin.restype = C.c_int
     lib.gfk_thin_max_topics.argtypes = []
     lib.gfk_thin_max_topics.restype = C.c_int
+    lib.gfk_wmd_dist_struct_size.restype = C.c_size_t
+    lib.gfk_wmd_struct_size.restype = C.c_size_t
+    if lib.gfk_wmd_dist_struct_size() != C.sizeof(GfkWmdDist):
+        raise RuntimeError("GfkWmdDist ABI mismatch")
+    if lib.gfk_wmd_struct_size() != C.sizeof(GfkWmd):
+        raise RuntimeError("GfkWmd ABI mismatch")
+    lib.gfk_wmd_dist.argtypes = [C.POINTER(GfkWmdDist), C.c_void_p]
+    lib.gfk_wmd_dist.restype = C.c_int
+    lib.gfk_wmd_solve.argtypes = [C.POINTER(GfkWmd), C.c_void_p]
+    lib.gfk_wmd_solve.restype = C.c_int
+    lib.gfk_wmd_max_words.argtypes = []
+    lib.gfk_wmd_max_words.restype = C.c_int
+    lib.gfk_wmd_grid.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int]
+    lib.gfk_wmd_grid.restype = C.c_int
+    lib.gfk_wmd_flow_len.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.gfk_wmd_flow_len.restype = C.c_int64
     for name, args in _EXTRA.items():
         if hasattr(lib, name):
             f = getattr(lib, name)
