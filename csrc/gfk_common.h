@@ -463,7 +463,8 @@ __device__ __forceinline__ uint4 philox(uint32_t k0, uint32_t k1, uint4 c) {
 // Stream tags keep the draws of different random tensors independent.
 enum : uint32_t { RNG_EPS = 1, RNG_DROP_ENC = 2, RNG_DROP_THETA = 3, RNG_INFER = 4,
                   RNG_RRELU = 5,     // RNG_RRELU | (layer << 8): one stream per hidden layer
-                  RNG_THIN = 6 };    // RNG_THIN | (token block << 8): csrc/thin.hip
+                  RNG_THIN = 6,      // RNG_THIN | (token block << 8): csrc/thin.hip
+                  RNG_GIBBS = 7 };   // RNG_GIBBS | (token block << 8): csrc/gibbs.hip
 
 __device__ __forceinline__ uint4 rng4(uint64_t seed, uint32_t step, uint32_t tag, uint32_t idx) {
   return philox((uint32_t)seed, (uint32_t)(seed >> 32), make_uint4(idx, step, tag, 0x5eedu));

@@ -35,7 +35,7 @@ from ..utils.config import load_config, model_kwargs_from_params
 def train_one(texts: List[str], n_topics: int, params: Dict, out_dir: str, device,
               trainer: str = "avitm", embeddings: Optional[np.ndarray] = None, n_words: int = 300,
               seed: int = 0) -> Dict:
-    from ..models import AVITM, CombinedTM
+    from ..models import AVITM, CombinedTM, GibbsLDA
     vocab = local_vocabulary(texts)
     X = vectorize(texts, vocab)
     id2token = {i: t for t, i in vocab.items()}
@@ -47,6 +47,12 @@ def train_one(texts: List[str], n_topics: int, params: Dict, out_dir: str, devic
             raise ValueError("the ctm trainer needs an embeddings column")
         tm = CombinedTM(input_size=len(vocab), contextual_size=embeddings.shape[1], device=device, **kw)
         ds = CTMDataset(embeddings, X, id2token)
+    elif trainer == "gibbs":
+        tm = GibbsLDA(n_components=n_topics, alpha=float(params.get("alpha", 5.0)),
+                      num_iterations=int(params.get("num_iterations", 1000)),
+                      optimize_interval=int(params.get("optimize_interval", 10)), seed=seed,
+                      device=device)
+        ds = BOWDataset(X, id2token)
     else:
         tm = AVITM(input_size=len(vocab), device=device, **kw)
         ds = BOWDataset(X, id2token)
@@ -109,7 +115,7 @@ def main(argv=None):
     p = argparse.ArgumentParser(description="collaborative vs non-collaborative models")
     p.add_argument("--path_corpus", required=True)
     p.add_argument("--models_folder", required=True)
-    p.add_argument("--trainer", default="avitm", choices=["avitm", "ctm"])
+    p.add_argument("--trainer", default="avitm", choices=["avitm", "ctm", "gibbs"])
     p.add_argument("--iters", type=int, default=1)
     p.add_argument("--start", type=int, default=0)
     p.add_argument("--ntopics_nodes", type=str, default=None)

@@ -10,7 +10,10 @@ run in-process (the fused HIP engine on a GPU):
   trainer "avitm"  ProdLDA / NeuralLDA (``model_type`` of the parameters)
   trainer "ctm"    CombinedTM when the corpus has an ``embeddings`` column, else the
                    AVITM model of ``model_type``
-  trainer "mallet" not available (no Java / Mallet in this stack): raises
+  trainer "gibbs"  GibbsLDA: the collapsed Gibbs sampler Mallet runs (csrc/gibbs.hip on a
+                   GPU, its numpy twin otherwise), configured by Mallet's fields
+  trainer "mallet" not available (no Java / Mallet in this stack): raises; "gibbs" is
+                   the native sampler
 
 Model folder (the topicmodeler layout the reference reads back, tm_wrapper.py:200-400):
 
@@ -19,7 +22,8 @@ Model folder (the topicmodeler layout the reference reads back, tm_wrapper.py:20
   {model}/corpus.parquet        training corpus (root: the given corpus; submodel: derived)
   {model}/TMmodel/betas.npy     [K, V] topic-word distributions
   {model}/TMmodel/thetas.npz    [D, K] sparse doc-topic matrix (3e-3 threshold, L1)
-  {model}/TMmodel/alphas.npy    [K] mean document-topic proportion
+  {model}/TMmodel/alphas.npy    [K] mean document-topic proportion ("gibbs": the
+                                sampler's Dirichlet prior alpha_k)
   {model}/TMmodel/vocab.txt     the model vocabulary, one term per line
   {model}/TMmodel/tpc_descriptions.txt   top words of every topic, one line per topic
   {model}/TMmodel/topic_coherence.npy    NPMI of every topic on the training corpus
@@ -160,7 +164,7 @@ class TMWrapper:
     def _get_model_config(self, trainer: str, TMparam: dict, hierarchy_level: int,
                           htm_version: Optional[str], expansion_tpc: Optional[int],
                           thr: Optional[float]) -> dict:
-        fields = (MALLET_FIELDS if trainer == "mallet" else CTM_FIELDS) + EXTRA_FIELDS
+        fields = (MALLET_FIELDS if trainer in ("mallet", "gibbs") else CTM_FIELDS) + EXTRA_FIELDS
         return {"trainer": trainer,
                 "TMparam": {t: TMparam[t] for t in fields if t in TMparam},
                 "hierarchy-level": hierarchy_level, "htm-version": htm_version,
@@ -200,12 +204,24 @@ class TMWrapper:
         trainer = cfg["trainer"]
         if trainer == "mallet":
             raise NotImplementedError("the Mallet (Gibbs LDA) trainer is not available in this "
-                                      "stack; use trainer='avitm' or 'ctm'")
+                                      "stack; use trainer='gibbs' (the native Gibbs sampler), "
+                                      "'avitm' or 'ctm'")
         texts = df["bow_text"].tolist()
         vocab = local_vocabulary(texts)
         terms = sorted(vocab, key=vocab.get)
         X = vectorize(texts, vocab)
         id2tok = dict(enumerate(terms))
+        if trainer == "gibbs":
+            from ..models import GibbsLDA
+            p = cfg["TMparam"]
+            tm = GibbsLDA(n_components=int(p.get("ntopics", p.get("n_components", 10))),
+                          alpha=float(p.get("alpha", 5.0)),
+                          num_iterations=int(p.get("num_iterations", 1000)),
+                          optimize_interval=int(p.get("optimize_interval", 10)),
+                          seed=self.seed, device=self.device)
+            ds = BOWDataset(X, id2tok)
+            tm.fit(ds)
+            return tm, ds, terms, X
         kw = self._model_kwargs(cfg["TMparam"])
         torch.manual_seed(self.seed)
         if trainer == "ctm" and "embeddings" in df.columns:
@@ -227,7 +243,9 @@ class TMWrapper:
         th = sp.csr_matrix(thetas.astype(np.float32))
         np.save(d / "betas.npy", betas)
         sp.save_npz(d / "thetas.npz", th)
-        np.save(d / "alphas.npy", np.asarray(th.mean(axis=0)).ravel())
+        prior = getattr(tm, "alphas", None)        # GibbsLDA: the sampler's alpha
+        np.save(d / "alphas.npy", np.asarray(th.mean(axis=0)).ravel() if prior is None
+                else np.asarray(prior))
         (d / "vocab.txt").write_text("\n".join(terms) + "\n", encoding="utf-8")
         top = np.argsort(-betas, axis=1)
         (d / "tpc_descriptions.txt").write_text(

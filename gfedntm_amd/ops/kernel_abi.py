@@ -252,6 +252,21 @@ class GfkWmd(C.Structure):
                 ("max_a", C.c_int32), ("max_b", C.c_int32), ("cap", C.c_int32),
                 ("max_grid", C.c_int32)]
 
+
+class GfkLda(C.Structure):
+    """collapsed Gibbs LDA launch: init / sweep / recount / merge (csrc/gibbs.hip)."""
+    _fields_ = [("indptr", P), ("indices", P), ("tok_ptr", P), ("z", P), ("nwk0", P), ("nk0", P),
+                ("alpha", P), ("ndk", P), ("inv", P), ("item_lo", P), ("item_hi", P),
+                ("item_row", P), ("mrg_word", P), ("mrg_first", P), ("mrg_n", P),
+                ("nwk", P), ("part", P),
+                ("seed", C.c_uint64), ("beta", C.c_float), ("vbeta", C.c_float),
+                ("n_docs", C.c_int32), ("n_items", C.c_int32), ("K", C.c_int32), ("V", C.c_int32),
+                ("doc0", C.c_int32), ("sweep", C.c_int32), ("frozen", C.c_int32),
+                ("pass_", C.c_int32), ("max_grid", C.c_int32)]
+
+
+LDA_INIT, LDA_SWEEP, LDA_RECOUNT, LDA_MERGE = 1, 2, 3, 4
+
 # optional entry points: name -> (argtypes, restype)
 _EXTRA = {
     "gfk_theta_infer": ([C.POINTER(GfkModel), C.POINTER(GfkInfer), C.c_void_p], C.c_int),
@@ -347,6 +362,15 @@ def declare(lib: C.CDLL) -> None:
     lib.gfk_wmd_grid.restype = C.c_int
     lib.gfk_wmd_flow_len.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.gfk_wmd_flow_len.restype = C.c_int64
+    lib.gfk_lda_struct_size.restype = C.c_size_t
+    if lib.gfk_lda_struct_size() != C.sizeof(GfkLda):
+        raise RuntimeError("GfkLda ABI mismatch")
+    lib.gfk_lda.argtypes = [C.POINTER(GfkLda), C.c_void_p]
+    lib.gfk_lda.restype = C.c_int
+    lib.gfk_lda_max_topics.argtypes = []
+    lib.gfk_lda_max_topics.restype = C.c_int
+    lib.gfk_lda_max_doc_tokens.argtypes = []
+    lib.gfk_lda_max_doc_tokens.restype = C.c_int
     for name, args in _EXTRA.items():
         if hasattr(lib, name):
             f = getattr(lib, name)

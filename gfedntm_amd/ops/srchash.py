@@ -23,7 +23,8 @@ CSRC = os.path.join(ROOT, "csrc")
 # under tolerances, never bitwise.
 KERNEL_SRCS = ["ctx.hip", "encoder.hip", "posterior.hip", "prodlda.hip", "neurallda.hip",
                "update.hip", "adam.hip", "comm.hip", "infer.hip", "score.hip", "cooc.hip",
-               "thin.hip", "simscore.hip", "wmd.hip", "step.cpp"]
+               "thin.hip", "simscore.hip", "wmd.hip", "gibbs.hip",
+               "step.cpp"]
 KFLAGS = ["-O3", "-fPIC", "-std=c++17", "-munsafe-fp-atomics", "-Wno-unused-result",
           "-fno-hip-fp32-correctly-rounded-divide-sqrt", "-fgpu-approx-transcendentals"]
 
