@@ -1045,6 +1045,34 @@ class FusedEngine(EngineBase):
         return "bf16" if m.mm_bf16 and (m.stage_flags & rs) == rs else "fp32"
 
     @property
+    def gemm_dtypes(self) -> Dict[str, Optional[str]]:
+        """Operand precision of each GEMM of the step, as the launchers choose it (read-only; it
+        restates csrc/prodlda.hip gfk_launch_prodlda_fwd / _bwd, csrc/neurallda.hip and
+        ``ctx_gemm_dtype``): "dec_fwd" (ProdLDA theta_d beta; NeuralLDA theta_d beta_sm),
+        "dthetad" (ProdLDA dlogit beta^T, both operands; NeuralLDA g beta_sm^T, beta_sm only),
+        "dbeta" (ProdLDA theta_d^T dlogit; NeuralLDA g^T theta_d), "ctx_a" / "ctx_z0"
+        (CombinedTM's x_ctx Wa^T and A Wc^T; None without them).  matmul_dtype = "bf16" rounds
+        them all except: the pipelined ProdLDA backward keeps fp32 operands in both its GEMMs;
+        the large-batch ProdLDA plan has no bf16 instance at all (NeuralLDA's kernels read
+        mm_bf16 themselves, at any batch size); the contextual GEMMs round only in the
+        register-streamed forward."""
+        m = self._m
+        on = bool(m.mm_bf16)
+        prod = m.kind == abi.KIND_PRODLDA
+        if prod and self.large_batch:
+            on = False
+        bwd = on
+        if on and prod:
+            kq4 = m.n_dpart < m.n_tiles and -(-int(m.K) // 16) >= 4
+            pipe = (kq4 and m.bwd_pre == 3 and m.bmax == 64 and m.ldb % 64 == 0
+                    and int(m.K) * int(m.ldb) * 4 < 0x7FFF0000)
+            bwd = not pipe
+        name = lambda b: "bf16" if b else "fp32"  # noqa: E731
+        ctx = self.ctx_gemm_dtype
+        return {"dec_fwd": name(on), "dthetad": name(bwd), "dbeta": name(bwd),
+                "ctx_a": ctx, "ctx_z0": ctx}
+
+    @property
     def launch_plan(self) -> str:
         """The launch plan in one phrase (recorded in bench / metrics records)."""
         if self.large_batch:

@@ -519,7 +519,9 @@ def test_bf16_decoder_matches_emulated_oracle(K, V):
     extra rounding of dlogit is inside the gradient tolerance).  The forward is the bf16
     strip kernel (32-k steps: 8, 16 or 32 pairs, a ring of 8); V = 80k: waves with a
     second strip (the ring's cross-strip slots).  At V = 40k / 80k the backward is the
-    pipelined kernel, whose GEMMs keep fp32 operands in bf16 mode (HBM-bound)."""
+    pipelined kernel, whose GEMMs keep fp32 operands in bf16 mode (HBM-bound).
+    (Step 0, full batches and a loose gradient tolerance only: the float64 walk of
+    tests/test_bf16_walk_gpu.py holds every bf16 instance to the fp32 rule over an epoch.)"""
     from gfedntm_amd.models.functional import encoder_forward
     from gfedntm_amd.models.networks import kl_terms, reconstruction_terms
     import torch.nn.functional as F
@@ -854,7 +856,8 @@ def test_postfold_matches_separate_post_fwd(monkeypatch, B, K, V, dtype):
     heads, reparameterisation, softmax, dropout, KL, running statistics and the optimizer
     step counters computed in its theta_d staging; post_fwd not launched) matches the
     separate post_fwd kernel over several fused-update graph replays -- same workspace
-    outputs for the backward, same counters, same trained state."""
+    outputs for the backward, same counters, same trained state.  (The bf16 strip with the
+    fold against float64: tests/test_bf16_walk_gpu.py case D.)"""
     from gfedntm_amd.ops.engine import STAGE_FWD_POSTFOLD
     kw = dict(input_size=V, n_components=K, hidden_sizes=(50, 50), batch_size=B,
               verbose=False, device="cuda")
@@ -910,7 +913,9 @@ def test_ctm_bf16_contextual_matches_emulated_oracle(V):
     fp32 accumulation) and the decoder's theta_d beta take bf16 operands; master weights,
     Adam state and every other op stay fp32.  Oracle: the fp32 PyTorch step with exactly
     those operands rounded to bf16 (C = 768, K = 100; V = 6k / 40k / 99k -- the BASELINE
-    CombinedTM class).  Reference: ctm inference_network.py:160-185."""
+    CombinedTM class).  Reference: ctm inference_network.py:160-185.
+    (Step 0, full batches and a loose gradient tolerance only: the float64 walk of
+    tests/test_bf16_walk_gpu.py holds every bf16 instance to the fp32 rule over an epoch.)"""
     import torch.nn.functional as F
     from gfedntm_amd.models import CombinedTM
     from gfedntm_amd.models.networks import kl_terms, reconstruction_terms
@@ -981,7 +986,9 @@ def test_bf16_neurallda_matches_emulated_oracle(K, V):
     beta_sm (lda_row: per non-zero dot products, fp32 accumulation; the same bf16 beta_sm in
     d theta_d) and the backward's coefficient x theta_d product (lda_beta_bwd) on bf16
     operands.  Oracle: the fp32 step with theta_d and beta_sm rounded to bf16 before their
-    product (reference decoder_network.py:127-132)."""
+    product (reference decoder_network.py:127-132).
+    (Step 0, full batches and a loose gradient tolerance only: the float64 walk of
+    tests/test_bf16_walk_gpu.py holds every bf16 instance to the fp32 rule over an epoch.)"""
     import torch.nn.functional as F
     from gfedntm_amd.models.functional import encoder_forward
     from gfedntm_amd.models.networks import kl_terms, reconstruction_terms
