@@ -44,141 +44,24 @@ from ..utils.flat import ALIGN, slot_view
 from ..utils.misc import graph_capture
 from . import kernel_abi as abi
 from . import native
+from . import plan
+# the launch plan lives in ops/plan.py; its names stay importable from here
+from .plan import (BETA_PAD, BETA_PAD_MIN_V, BMAX_CHOICES, BWD8_LDS, LB_MIN_BMAX,  # noqa: F401
+                   LDS_LIMIT, POST_ROWS_AUTO, STAGE_BWD_BATCH8, STAGE_CTX_BWDPP, STAGE_CTX_FULL,
+                   STAGE_CTX_RS, STAGE_FWD_POSTFOLD, STAGE_FWD_STRIP, STAGE_LB, STAGE_PLANS,
+                   STAGE_POST_JOINT, STAGE_POST_ROWS2, STAGE_POST_ROWS4, STAGE_WIN_BATCH8,
+                   STAGE_WIN_SPARSE, STAGE_WIN_WAVES6, UPDATE_FUSED, UPDATE_GRAD, VB, WIN6_LDS,
+                   beta_ld, bwd8_lds_bytes, bwd_batch8_flag, bwd_kq, engine_bmax, post_rows_flags,
+                   theta_stride, uses_large_batch_plan, win_waves_flag)
 
-BMAX_CHOICES = (16, 32, 64, 128, 256, 512)
-# batch sizes above this run the large-batch plan (csrc/gfk_common.h GFK_LB)
-LB_MIN_BMAX = 256
-LDS_LIMIT = 160 * 1024
 # rows of every contextual GEMM of theta inference (_ctx_dense): the smallest default chunk, so
 # CombinedTM's [rows, V] adapt_bert output stays within that chunk's budget
 CTX_INFER_ROWS = 256
-VB = 64
-# stage_flags plans, fastest first: bit 0 = MLP weights staged in LDS (enc_in,
-# post_bwd); bit 1 = the posterior kernels read the [B, K] batch matrices from L2
-# instead of staging them (large K).  Plan 3 (weights staged, batch matrices from L2)
-# is the large-K plan: the head weights [K, H] feed post_bwd's GEMVs from LDS instead
-# of one dependent L2 round trip per pass
-STAGE_PLANS = (1, 0, 3, 2)
-STAGE_FWD_STRIP = 4               # bit 2: ProdLDA strip forward (csrc/prodlda.hip)
-STAGE_WIN_SPARSE = 16             # bit 4: sparse W_in tiles (csrc/update.hip win_tile_sparse)
-STAGE_CTX_FULL = 32               # bit 5: CombinedTM forward, one workgroup per tile (csrc/ctx.hip)
-STAGE_WIN_BATCH8 = 512            # bit 9: batched launches: win_update's 8-wave tile shape
-STAGE_CTX_BWDPP = 4096            # bit 12: CombinedTM backward, persistent pipelined shape (csrc/ctx.hip)
-STAGE_CTX_RS = 32768              # bit 15: CombinedTM forward, Wa register-streamed (csrc/ctx.hip)
-STAGE_FWD_POSTFOLD = 65536        # bit 16: the strip forward computes post_fwd (csrc/prodlda.hip FP)
-STAGE_LB = 524288                 # bit 19: the large-batch plan (bmax 256 / 512, csrc/gfk_common.h)
-STAGE_POST_ROWS2 = abi.POST_ROWS2  # bit 20: batched post_bwd, two rows per workgroup; its batch-level
-                                   #         workgroup in row_bwd (csrc/posterior.hip)
-STAGE_POST_JOINT = abi.POST_JOINT  # bit 21: ... the rows through each phase together (with bit 20)
-STAGE_POST_ROWS4 = abi.POST_ROWS4  # bit 22: ... four rows per workgroup (with bits 20 and 21)
-STAGE_BWD_BATCH8 = abi.BWD_BATCH8  # bit 23: batched ProdLDA tile backward, 8-wave workgroups, three per CU
-STAGE_WIN_WAVES6 = abi.WIN_WAVES6  # bit 24: batched win_update (with bit 9), 6 waves per SIMD, three per CU
-# the LDS one of a CU's three 8-wave backward workgroups may take (csrc/prodlda.hip BWD8_LDS)
-BWD8_LDS = LDS_LIMIT // 3
-# ... and one of its three 6-waves-per-SIMD win_update workgroups
-WIN6_LDS = LDS_LIMIT // 3
-# the shape GFEDNTM_POST_ROWS=auto takes where bit 20 applies (a key of abi.POST_ROWS_SHAPES):
-# the headline's interleaved A/B, 8 clients K = 50 (profiles/r7/ab_post_rows.txt): serial2
-# 0.1176 ms per round, two joint rows 0.1159, four 0.1193
-POST_ROWS_AUTO = "2"
-# (removed in round 6, measured not faster: bits 3 / 8 the strip forward's 8-wave whole-block
-# prefetch vs its ring (now the only variant), bit 6 the plain rolling prefetch, 7 the split W_in update, 10 the sparse tile's register second moment
-# as a knob, 11 / 13 the LDS-DMA balanced CombinedTM forwards, 14 the persistent Wc update,
-# 17 the moved batch-level workgroup on its own, 18 the one-range backward walking tiles)
 
 
-def post_rows_flags(n_clients: int, bmax: int, cus: int, knob: str = "auto") -> int:
-    """stage_flags bits of a batched launch's post_bwd shape (GFEDNTM_POST_ROWS).
-
-    ``auto``: where M clients' bmax + 1 one-row workgroups exceed one round of the CUs, the
-    shape POST_ROWS_AUTO; else none (the one-row shape).  ``serial2`` / ``2`` / ``4`` force
-    that shape on every launch of M > 1 clients, whatever the CU count."""
-    if n_clients < 2:
-        return 0
-    if knob == "auto":
-        return abi.POST_ROWS_SHAPES[POST_ROWS_AUTO] if n_clients * (bmax + 1) > cus else 0
-    if knob not in abi.POST_ROWS_SHAPES:
-        raise ValueError(f"GFEDNTM_POST_ROWS={knob!r}: expected auto, serial2, 2 or 4")
-    return abi.POST_ROWS_SHAPES[knob]
-
-
-def bwd_kq(n_tiles: int, n_dpart: int, K: int) -> int:
-    """k ranges of ProdLDA's tile backward (csrc/prodlda.hip bwd_kq)."""
-    return 4 if n_dpart < n_tiles and -(-K // 16) >= 4 else 1
-
-
-def bwd8_lds_bytes(bmax: int, K: int, kt: int) -> int:
-    """Dynamic LDS of the 8-wave tile backward (csrc/prodlda.hip bwd8_smem): theta_d, the
-    region of the logit tile and then the beta block, the logit gradient, lse / S / rstd."""
-    kpq = -(-K // 16) * 16
-    return 4 * (bmax * kt + max(bmax * VB, kpq * 66) + bmax * 66 + 2 * bmax + VB)
-
-
-def bwd_batch8_flag(n_clients: int, n_tiles: int, cus: int, *, bmax: int, K: int, bf16: bool,
-                    kq: int, bwd_pre: int, lds_bytes: int, knob: str = "auto") -> int:
-    """stage_flags bit of a batched launch's ProdLDA tile backward (GFEDNTM_BWD_WAVES).
-
-    The 8-wave instance exists for the one-range tile backward (``kq`` = 1 -- 0 where the
-    model runs no tile backward at all --, no precomputed logit gradient) at bmax = 64,
-    K <= 64, fp32, within a third of a CU's LDS.  ``auto``: where M clients' tiles are more
-    than two 16-wave workgroups per CU hold at once and at most the three 8-wave ones do
-    (2 CUs < M n_tiles <= 3 CUs: one round instead of two).  ``8`` / ``16`` force the shape
-    on every launch of M > 1 clients; ``8`` without an instance is an error."""
-    if knob not in ("auto", "16", "8"):
-        raise ValueError(f"GFEDNTM_BWD_WAVES={knob!r}: expected auto, 16 or 8")
-    if n_clients < 2 or knob == "16":
-        return 0
-    exists = (kq == 1 and not bwd_pre and bmax == 64 and K <= 64 and not bf16
-              and lds_bytes <= BWD8_LDS)
-    if knob == "8":
-        if not exists:
-            raise RuntimeError("GFEDNTM_BWD_WAVES=8: no 8-wave tile backward for this launch "
-                               "(one-range fp32 tile backward, bmax 64, K <= 64, LDS <= %d B)" % BWD8_LDS)
-        return STAGE_BWD_BATCH8
-    return STAGE_BWD_BATCH8 if exists and 2 * cus < n_clients * n_tiles <= 3 * cus else 0
-
-
-def win_waves_flag(n_clients: int, n_wg: int, cus: int, *, dense: bool, batch8: bool, fused: bool,
-                   H0: int, lds_bytes: int, knob: str = "auto") -> int:
-    """stage_flags bits of a batched launch's win_update register budget (GFEDNTM_WIN_WAVES).
-
-    The 8-wave dense tile kernel (stage bit 9) is compiled for 8 waves per SIMD (64 VGPRs,
-    which it exceeds: it spills) and, as a second instance (bit 24), for 6 (80 VGPRs, three
-    workgroups per CU).  That instance exists for launches of M > 1 clients whose W_in
-    gradient runs as dense tiles (``dense``: no sparse tiles, not the large-batch plan), with
-    fused updates, H0 <= 64, within a third of a CU's LDS.  ``n_wg``: a client's workgroups
-    (tiles, contextual tiles, weight and vector jobs, the next-batch workgroup).  ``auto``:
-    bit 24 where the launch takes the 8-wave shape anyway (``batch8``) and three workgroups
-    per CU hold every client's at once (M n_wg <= 3 CUs), so the lower occupancy costs no
-    second round.  ``6`` / ``8`` force the 8-wave shape at that budget on every launch of
-    M > 1 clients with dense tiles (bit 9, and bit 24 for ``6``); ``6`` without an instance
-    is an error."""
-    if knob not in ("auto", "8", "6"):
-        raise ValueError(f"GFEDNTM_WIN_WAVES={knob!r}: expected auto, 8 or 6")
-    if n_clients < 2:
-        return 0
-    exists = bool(dense) and bool(fused) and H0 <= 64 and lds_bytes <= WIN6_LDS
-    if knob == "8":
-        return STAGE_WIN_BATCH8 if dense else 0
-    if knob == "6":
-        if not exists:
-            raise RuntimeError("GFEDNTM_WIN_WAVES=6: no 6-waves-per-SIMD win_update for this launch "
-                               "(dense W_in tiles, fused updates, H0 <= 64, LDS <= %d B)" % WIN6_LDS)
-        return STAGE_WIN_BATCH8 | STAGE_WIN_WAVES6
-    return STAGE_WIN_WAVES6 if exists and batch8 and n_clients * n_wg <= 3 * cus else 0
-
-
-def engine_bmax(tm) -> int:
-    """Rows the engine's workspaces are sized for: the batch size rounded up to a kernel
-    instance.  (K > 256 runs the large-batch plan at the batch's own size since round 6;
-    round 5 padded it to 256 rows.)"""
-    return next(x for x in BMAX_CHOICES if x >= tm.batch_size)
-
-
-def uses_large_batch_plan(tm, bmax: int) -> bool:
-    """The large-batch plan (csrc/gfk_common.h GFK_LB): 256 / 512 rows, or K > 256 (its
-    posterior / decoder shapes take K <= 512) at any batch size."""
-    return bmax >= LB_MIN_BMAX or tm.n_components > 256
+def lds_required(tm, bmax: int) -> int:
+    """Largest dynamic LDS any fused kernel needs for this model (plan.lds_required)."""
+    return plan.lds_required(native.kernels(), tm, bmax)
 
 
 def _explain(ok: bool, why: str, explain: bool) -> bool:
@@ -267,86 +150,12 @@ def score_covers(tm, explain: bool = False) -> bool:
     return True
 
 
-UPDATE_GRAD, UPDATE_FUSED = 0, 1
-
-
 def _max_grid(max_grid) -> int:
     """A caller's cap on a launch's workgroups (csrc: the max_grid fields), checked."""
     g = int(max_grid)
     if g < 1:
         raise ValueError("max_grid must be a positive number of workgroups")
     return g
-
-
-def theta_stride(K: int) -> int:
-    """Row stride of the dropped-out theta workspace: K rounded up to 2 x odd, so the
-    decoder MFMAs' A-role reads (16 rows x 2 k per half-wave, ds_read_b32: bank =
-    dword % 32) land on 32 distinct banks (B * kt stays a multiple of 4 for LDS-DMA)."""
-    kt = -(-K // 2) * 2
-    return kt + 2 if (kt // 2) % 2 == 0 else kt
-
-
-# beta rows padded to whole 64-column tiles (256 B) from this vocabulary size on
-# (utils/flat.py): the large-V kernels' RMW tiles never split a cache line with another
-# tile, and a tile's columns past V are row padding (prodlda_bwd_pipe_kernel stores there)
-BETA_PAD_MIN_V = 8192
-BETA_PAD = 64                     # whole 64-column tiles (the pipelined backward's stores rely on it)
-
-
-def beta_ld(V: int) -> int:
-    """beta's row stride in the fused engine's flat layout."""
-    return -(-V // BETA_PAD) * BETA_PAD if V >= BETA_PAD_MIN_V else V
-
-
-def _shape_model(tm, bmax: int) -> "abi.GfkModel":
-    m = abi.GfkModel()
-    hs = list(tm.hidden_sizes)
-    m.bmax, m.V, m.K, m.n_hidden = bmax, tm.input_size, tm.n_components, len(hs)
-    m.ldb = beta_ld(m.V)
-    for i, h in enumerate(hs):
-        m.H[i] = h
-    m.kind = abi.KIND_PRODLDA if tm.model_type.lower() == "prodlda" else abi.KIND_LDA
-    m.mm_bf16 = int(getattr(tm, "matmul_dtype", "fp32") == "bf16")
-    m.kt = theta_stride(m.K)
-    m.vb, m.n_tiles = VB, -(-m.V // VB)
-    m.n_dpart = m.n_tiles if m.kind == abi.KIND_PRODLDA else 1
-    return m
-
-
-def _force_k_split(lib, m) -> bool:
-    """ProdLDA backward at large K with few vocab tiles: the one-range shape (a workgroup
-    per tile, all K topics of theta_d and the beta tile in LDS) exceeds the LDS at
-    K = 256, B >= 64.  Then use the 4-k-range shape anyway (persistent, n_dpart < n_tiles
-    slabs; ~71 KB at K = 256).  Returns True when it set n_dpart so."""
-    if m.kind != abi.KIND_PRODLDA or m.n_tiles < 2 or -(-m.K // 16) < 4:
-        return False
-    m.n_dpart = m.n_tiles
-    if lib.gfk_smem_required(C.byref(m), 1) <= LDS_LIMIT:
-        return False
-    m.n_dpart = m.n_tiles - 1
-    return True
-
-
-def lds_required(tm, bmax: int) -> int:
-    """Largest dynamic LDS any fused kernel needs for this model (weights unstaged),
-    as computed by the kernel library itself."""
-    m = _shape_model(tm, bmax)
-    lib = native.kernels()
-    which = (0, 1) if m.kind == abi.KIND_PRODLDA else (2, 3)
-    if uses_large_batch_plan(tm, bmax):
-        need = 0
-        for win in (0, STAGE_WIN_SPARSE):        # (either W_in tile shape)
-            m.stage_flags, m.n_dpart = 2 | STAGE_LB | win, 1
-            need = max(need, int(max(lib.gfk_smem_required(C.byref(m), w) for w in which + (4, 5, 7))))
-        return need
-    _force_k_split(lib, m)
-    need = 0
-    for flags in (0, 2):                 # weights unstaged; batch matrices in LDS, then in L2
-        m.stage_flags = flags
-        need = int(max(lib.gfk_smem_required(C.byref(m), w) for w in which + (4, 5, 7)))
-        if need <= LDS_LIMIT:
-            break
-    return need
 
 
 # Per solver: hyperparameters as the reference constructs the torch optimizer
@@ -461,7 +270,7 @@ class FusedEngine(EngineBase):
         self.adam_pow = torch.ones(2, dtype=torch.float64, device=dev)     # beta1^t, beta2^t
         self.adam_coef = torch.zeros(2, dtype=torch.float32, device=dev)   # see csrc/gfk_common.h
         # CTM contextual path on the fused kernels: CombinedTM (ctx_fwd / ctx_bwd) and
-        # ZeroShotTM (dense input layer in enc_in / win_update).  _plan_ctx may fall back
+        # ZeroShotTM (dense input layer in enc_in / win_update).  The plan (ops/plan.py) may fall back
         # to host-issued GEMMs for shapes outside the kernels' plan; that path runs in
         # gradient mode with the generic optimizer kernel
         self.ctx_fused = tm.kind == "ctm"
@@ -553,42 +362,26 @@ class FusedEngine(EngineBase):
     def _fill_static(self):
         tm, m, model = self.tm, self._m, self.model
         net = model.inf_net
-        hs = list(tm.hidden_sizes)
-        m.bmax, m.V, m.K, m.n_hidden = self.bmax, tm.input_size, tm.n_components, len(hs)
-        # beta's row stride (a padded slot: rows start on 128-B lines, utils/flat.py)
+        # 1. the value fields (beta's row stride: a padded slot, rows start on 128-B lines,
+        # utils/flat.py)
         bs = self.flat.slots.get("beta")
-        m.ldb = int(bs.ld or bs.shape[1]) if bs is not None else int(m.V)
-        for i, h in enumerate(hs):
-            m.H[i] = h
-        m.act = abi.ACT_CODES[tm.activation]
-        m.mm_bf16 = int(getattr(tm, "matmul_dtype", "fp32") == "bf16")
-        m.kind = abi.KIND_PRODLDA if model.is_prodlda else abi.KIND_LDA
-        if self.kind == "ctm":
-            m.input = abi.IN_COMBINED if tm.inference_type == "combined" else abi.IN_CONTEXTUAL
-            m.C = tm.contextual_size
-        else:
-            m.input = abi.IN_BOW
-        # CTM label head: the labels are the last L inputs of input_layer (CombinedTM
-        # [BoW | adapted | labels], ZeroShotTM [contextual | labels])
-        m.L = int(getattr(tm, "label_size", 0) or 0)
-        m.lab_on = int(m.L > 0)
-        if m.lab_on:
-            m.lab_off = 2 * tm.input_size if m.input == abi.IN_COMBINED else m.C
-        props = torch.cuda.get_device_properties(self.device)
-        if self.ctx_fused:
-            self._plan_ctx(props.multi_processor_count)
-        m.vb = VB
-        m.n_tiles = -(-m.V // VB)
-        m.dec_grid = int(min(m.n_tiles, 2 * props.multi_processor_count))
-        m.learn_priors = int(tm.learn_priors)
-        m.kt = theta_stride(m.K)
-        m.n_dpart = m.n_tiles if m.kind == abi.KIND_PRODLDA else 1
+        plan.fill_shape(m, tm, self.bmax, int(bs.ld or bs.shape[1]) if bs is not None else None)
         m.drop_enc = float(net.dropout_enc.p)
         m.drop_theta = float(model.drop_theta.p)
         m.bn_momentum = float(model.beta_batchnorm.momentum)
         m.bn_eps = float(model.beta_batchnorm.eps)
         m.kl_weight = float(self.beta_weight)
         m.seed = self.seed
+        # 2. the launch plan (ops/plan.py)
+        wa = self.flat.slots.get("inf_net.adapt_bert.weight")
+        sp = plan.plan_step(self.lib, m, torch.cuda.get_device_properties(self.device).multi_processor_count,
+                            plan.Knobs.from_env(), self.solver, self.flat.n_total,
+                            wa is None or wa.offset % 4 == 0)
+        self.postfold_ok = sp.postfold_ok
+        if sp.ctx_fallback is not None:
+            self._ctx_fallback(sp.ctx_fallback)
+        # 3. pointers
+        hs = list(tm.hidden_sizes)
         if m.lab_on:
             P0 = self.flat.buffer
             m.w_cls = self._ptr(P0, "label_classification.weight")
@@ -637,181 +430,11 @@ class FusedEngine(EngineBase):
         m.off_g = (self.grad.data_ptr() - P.data_ptr()) // 4
         m.adam_pow, m.adam_coef = self.adam_pow.data_ptr(), self.adam_coef.data_ptr()
         self._sync_opt_fields()
-        if self.large_batch:
-            self._plan_large_batch(props.multi_processor_count)
-            self._alloc_workspace()
-            rc = self.lib.gfk_setup(C.byref(m))
-            if rc:
-                raise RuntimeError(f"gfk_setup failed ({rc})")
-            return
-        which = (0, 1) if m.kind == abi.KIND_PRODLDA else (2, 3)
-        k_split = _force_k_split(self.lib, m)
-        need = lambda: max(self.lib.gfk_smem_required(C.byref(m), w)  # noqa: E731
-                           for w in which + (4, 5, 7, 8))
-        for flags in STAGE_PLANS:         # first plan that fits the 160 KiB of LDS
-            m.stage_flags = flags
-            if need() <= LDS_LIMIT:
-                break
-        else:
-            raise RuntimeError(f"fused step needs {need()} B of LDS (> {LDS_LIMIT})")
-        if m.kind == abi.KIND_PRODLDA:
-            # persistent decoder forward: one workgroup per resident slot (16-wave
-            # workgroups: 2 per CU when the LDS allows), each looping over its vocab
-            # tiles with theta_d staged once and its row-LSE partials merged
-            cu = props.multi_processor_count
-            sm = self.lib.gfk_smem_required(C.byref(m), 0)
-            m.dec_grid = int(min(m.n_tiles, (2 if 2 * sm <= LDS_LIMIT else 1) * cu))
-            # strip forward (prodlda_fwd_strip_kernel, stage_flags bit 2): each wave owns
-            # 16 columns x all rows, beta straight into registers, batch norm without
-            # barriers.  The default wherever it applies (fp32, B <= 64): interleaved A/B
-            # vs the tile kernel (profiles/r2/ab_strip_forward.txt) K=50 headline 0.0583
-            # vs 0.0589 ms, K=50 V=28k 0.092 vs 0.101, K=200 V=112k 0.342 vs 0.349, CTM /
-            # ZeroShotTM K=100 neutral.  GFEDNTM_FWD_STRIP=0 selects the tile kernel
-            strip = os.environ.get("GFEDNTM_FWD_STRIP", "auto")
-            # (bf16 GEMMs: the ring variant with v_mfma_f32_16x16x32_bf16, 32-k steps)
-            fits = (m.bmax <= 64 and m.K <= 256 and m.K * m.ldb < (1 << 29))
-            if fits and strip in ("1", "auto"):
-                m.stage_flags |= STAGE_FWD_STRIP
-                # the rolling prefetch: the next strip's k pair loaded into the registers
-                # its MFMAs just consumed, through a ring of <= 13 pairs (K > 104: 128 VGPRs,
-                # 16 waves per CU; K = 200 V = 112k forward 39.7 -> 36.5 us, round 0.2794 ->
-                # 0.2751 ms).  Rounds 5-6 removed the other strip variants: the plain rolling
-                # one, the non-prefetching one and the 8-wave whole-block prefetch, measured
-                # slower (profiles/r3, r4, r6/ab_strip_pf_vs_ring.txt)
-                m.dec_grid = int(min(m.n_tiles, cu))
-                # the batch-coupled posterior (BN of the heads, reparameterisation, softmax,
-                # dropout, KL) inside the ring forward's theta_d staging: post_fwd is not
-                # launched (K <= 64, no label head; csrc/gfk_common.h gfk_postfold).  Where it
-                # pays: batched launches of several clients (BatchedSteps, sim8 strip forward
-                # + post_fwd 27.4 -> 20.5 us); for ONE client the redundant per-workgroup
-                # statistics lengthen the forward's critical path more than the launch they
-                # save (interleaved, one box: 0.0601 vs 0.0597 ms per round,
-                # profiles/r5/ab_fold.txt).  GFEDNTM_POSTFOLD=1 forces it here, =0 everywhere
-                self._postfold_ok = bool(m.K <= 64 and not m.lab_on)
-                if self._postfold_ok and os.environ.get("GFEDNTM_POSTFOLD", "auto") == "1":
-                    m.stage_flags |= STAGE_FWD_POSTFOLD
-            # backward: one workgroup per tile while the tiles fit the resident slots;
-            # else persistent, n_dpart d theta_d slabs: with >= 4 k tiles the topics
-            # are split over 4 workgroups per slab (csrc/prodlda.hip, 8 waves each, two
-            # per CU when their LDS allows), otherwise one 16-wave workgroup per CU
-            m.n_dpart = m.n_tiles
-            sb = self.lib.gfk_smem_required(C.byref(m), 1)      # one tile per workgroup
-            if m.n_tiles <= (2 if 2 * sb <= LDS_LIMIT else 1) * cu and not k_split:
-                m.n_dpart = m.n_tiles
-            elif -(-m.K // 16) >= 4:
-                m.n_dpart = min(cu // 2, m.n_tiles - 1)
-                if 2 * self.lib.gfk_smem_required(C.byref(m), 1) > LDS_LIMIT:
-                    m.n_dpart = min(cu // 4, m.n_tiles - 1)
-            else:
-                m.n_dpart = cu
-            # the persistent k-range backward (4 workgroups per vocab tile) takes its
-            # logit-gradient tiles precomputed once per tile by prodlda_dlogit instead of
-            # recomputing them in each range workgroup; GFEDNTM_BWD_PRE=0 selects the
-            # recomputing variant
-            kq4 = m.n_dpart < m.n_tiles and -(-m.K // 16) >= 4
-            # (2: two per CU; 3, the default: two per CU, software-pipelined -- the next
-            # tile's loads in flight during this tile's compute and stores -- where it
-            # applies: fp32, B = 64.  Round 6 removed the 80-VGPR three-per-CU shape and the
-            # split beta Adam pass, both measured slower: profiles/r2, profiles/r4)
-            pre = os.environ.get("GFEDNTM_BWD_PRE", "3")
-            m.bwd_pre = int(pre) if kq4 and m.bmax <= 64 and pre in ("2", "3") else 0
-            if (m.bwd_pre == 3 and m.bmax == 64 and m.ldb % 64 == 0
-                    and m.K * m.ldb * 4 < 0x7FFF0000):
-                pass
-            elif m.bwd_pre:
-                m.bwd_pre = 2            # two per CU, no register cap
-        # W_in tiles as entry lists instead of dense x^T MFMA tiles where a 64-word tile
-        # holds few non-zeros (large vocabularies, the 8-wave update shape: more tiles than
-        # two rounds of workgroups); GFEDNTM_WIN_SPARSE=0 keeps the dense tiles
-        cu_n = props.multi_processor_count
-        # CombinedTM at large V: ctx_fwd with all batch rows per vocab tile (each Wa block
-        # staged once instead of once per 16-row block); GFEDNTM_CTX_FULL=0 / 1 overrides
-        cf_env = os.environ.get("GFEDNTM_CTX_FULL", "auto")
-        # (matmul_dtype = "bf16": the register-streamed forward at any V -- the variant with
-        # bf16 operands on the matrix cores; the other shapes keep fp32 GEMMs)
-        if m.ctx_fused == 1 and m.bmax <= 64 and (
-                cf_env == "1" or (cf_env == "auto" and (m.n_tiles > 2 * cu_n or m.mm_bf16))):
-            m.stage_flags |= STAGE_CTX_FULL
-            # ... as the register-streamed persistent kernel: one 16-wave workgroup per CU
-            # owns an equal range of 16-column units (at most 32: V <= 131k on 256 CUs), Wa
-            # streamed from global memory into registers as the MFMA A operand, x_ctx staged
-            # once per workgroup in 256-float phases; each workgroup leaves one contextual z0
-            # partial (ctx_parts for enc_in).  V = 99k, interleaved: ctx_fwd 134 -> 122 us,
-            # round 0.7386 -> 0.7287 ms (profiles/r4/ab_s8).  GFEDNTM_CTX_RS=0 keeps the
-            # one-workgroup-per-tile kernel.  (Round 6 removed the LDS-DMA balanced shapes,
-            # bits 11 / 13, measured slower than this one.)
-            n_units = -(-int(m.V) // 16)
-            if (os.environ.get("GFEDNTM_CTX_RS", "1") != "0" and int(m.H[0]) <= 64
-                    and -(-n_units // min(m.n_tiles, cu_n)) <= 32
-                    and m.V * m.C * 4 < (1 << 31) and 4 * self.flat.n_total < (1 << 31)):
-                m.stage_flags |= STAGE_CTX_RS
-                m.ctx_parts = int(min(m.n_tiles, cu_n))
-        # CombinedTM backward as one persistent workgroup per CU walking equal ranges of the
-        # (tile, C chunk) items with the next item's Wa state in flight (csrc/ctx.hip
-        # gfk_ctx_bwd_pp_k); GFEDNTM_CTX_BWDPP=0 keeps the (tile, chunk) grid
-        if (m.ctx_fused == 1 and m.bmax <= 64 and int(m.H[0]) <= 64
-                and os.environ.get("GFEDNTM_CTX_BWDPP", "auto") in ("1", "auto")
-                and (os.environ.get("GFEDNTM_CTX_BWDPP", "auto") == "1" or m.n_tiles > 2 * cu_n)):
-            m.stage_flags |= STAGE_CTX_BWDPP
-            m.ctx_bgrid = int(cu_n)
-        ws_env = os.environ.get("GFEDNTM_WIN_SPARSE", "auto")
-        # (fused CombinedTM too: its bag-of-words half as sparse tiles, the contextual half
-        # as dense tiles of the same launch -- csrc/update.hip win_tile_ctx; B <= 64)
-        comb = m.input == abi.IN_COMBINED and m.ctx_fused == 1 and m.bmax <= 64
-        if (m.input == abi.IN_BOW or comb) and int(m.H[0]) <= 64 and m.bmax <= 128 and (
-                ws_env == "1" or (ws_env == "auto" and m.n_tiles > 4 * cu_n)):
-            m.stage_flags |= STAGE_WIN_SPARSE
-            # fused CombinedTM: the contextual half (Wc) as dense tiles of the same launch.
-            # (Round 6 removed three opt-in variants measured slower: Wc as a persistent
-            # kernel -- V = 99k, 0.7389 vs 0.7309 ms; the sparse tile's second moment in
-            # registers instead of LDS -- profiles/r3/win_vl/; the split W_in update, the
-            # words outside the batch on a side stream -- K=200 V=112k 0.320 vs 0.294 ms,
-            # profiles/r3/win_split.md)
+        # 4. workspaces, the kernels' dynamic-LDS limits
         self._alloc_workspace()
         rc = self.lib.gfk_setup(C.byref(m))
         if rc:
             raise RuntimeError(f"gfk_setup failed ({rc})")
-
-    def _plan_large_batch(self, cu: int):
-        """The large-batch plan, 128 < batch_size <= 512 (csrc/gfk_common.h GFK_LB; reference
-        avitm.py:84-85 takes any batch_size).  The row-parallel kernels (enc_in, post_fwd,
-        row_loss, row_bwd, post_bwd) run as for small batches with the [B, K] batch matrices
-        read from L2 (bit 1), W_in's gradient on the sparse tiles (bit 4), the weight jobs and
-        NeuralLDA's beta backward in 128-row chunks.  ProdLDA's decoder: logits = theta_d beta,
-        dbeta = theta_d^T dlogit and d theta_d = dlogit beta^T are hipBLASLt GEMMs on the step's
-        stream (PH_LB_GEMM_FWD / _BWD: at B >= 256 they are large enough to run near the
-        matrix cores' fp32 peak) around prodlda_lb_colbn (column batch-norm, BN'ed tiles, row
-        sum-exp partials) and prodlda_lb_dlogit (the logit gradient) -- one slab of d theta_d,
-        the [B, ldb] logit / logit-gradient matrix in ws["dt"].  Gradient mode: the generic
-        optimizer kernel updates every tensor (as the CTM host-GEMM path)."""
-        m = self._m
-        # W_in's gradient: the sparse entry-list tiles where a 64-word tile holds few of the
-        # batch's non-zeros (more tiles than 4 rounds of the CUs, as for small batches), else
-        # the dense tiles in 128-row chunks (csrc/update.hip win_tile_dense_ch);
-        # GFEDNTM_WIN_SPARSE=1 / 0 forces either
-        ws_env = os.environ.get("GFEDNTM_WIN_SPARSE", "auto")
-        sparse = ws_env == "1" or (ws_env == "auto" and m.n_tiles > 4 * cu)
-        m.stage_flags = 2 | STAGE_LB | (STAGE_WIN_SPARSE if sparse else 0)
-        m.dec_grid = int(min(m.n_tiles, 2 * cu))
-        m.n_dpart = 1
-        m.bwd_pre = 0
-        # ProdLDA's decoder on the matrix cores (csrc/prodlda.hip prodlda_lb_fwd / _bwd) at
-        # bmax 256, K <= 208: one 16-wave workgroup per CU, persistent over the tiles, the
-        # backward's d theta_d in one slab per workgroup.  Elsewhere (bmax 512, K > 208) and
-        # with GFEDNTM_LB_GEMM=1: the library GEMMs around the HIP kernels.
-        m.lb_fused = 0
-        if (m.kind == abi.KIND_PRODLDA and int(m.K) <= 208 and self.bmax == 256
-                and os.environ.get("GFEDNTM_LB_GEMM", "0") != "1"):
-            # (+ bit 2: beta's Adam step in prodlda_lb_bwd's epilogue -- the generic optimizer
-            # pass then skips beta, 80 % of the parameters at K = 200, V = 112k)
-            m.lb_fused = 3 | (4 if self.solver == "adam" else 0)
-            m.dec_grid = int(min(m.n_tiles, cu))
-            if m.lb_fused & 2:
-                m.n_dpart = m.dec_grid
-        which = (0, 1) if m.kind == abi.KIND_PRODLDA else (2, 3)
-        need = max(self.lib.gfk_smem_required(C.byref(m), w) for w in which + (4, 5, 7))
-        if need > LDS_LIMIT:
-            raise RuntimeError(f"large-batch plan needs {need} B of LDS (> {LDS_LIMIT})")
 
     def _lb_views(self):
         """(theta_d [B, K], beta [K, ldb], beta's gradient [K, ldb], the logit matrix
@@ -831,35 +454,6 @@ class FusedEngine(EngineBase):
         th, beta, gbeta, dt, dth = self._lb_views()
         torch.mm(th.t(), dt, out=gbeta)                  # dbeta = theta_d^T dlogit
         torch.mm(dt, beta.t(), out=dth)                  # d theta_d = dlogit beta^T
-
-    def _plan_ctx(self, cu: int):
-        """Fused CombinedTM contextual kernels (csrc/ctx.hip).  The forward runs one
-        workgroup per (vocab tile, 16-row block); the backward splits C into chunks
-        of 16k <= 256 floats, enough of them that n_tiles x chunks covers the CUs
-        once (one 16-wave workgroup per CU).  Falls back to the host GEMMs when a shape is outside
-        the kernels' assumptions (C % 4, H0 <= 512, LDS)."""
-        m = self._m
-        if m.input == abi.IN_CONTEXTUAL:
-            # ZeroShotTM: the [C, H0] input layer is gathered densely by enc_in and its
-            # gradient + Adam are ceil(C / 64) extra win_update tiles
-            m.ctx_fused = 2 if int(m.H[0]) <= 512 else 0
-            if not m.ctx_fused:
-                self._ctx_fallback(f"H0 = {int(m.H[0])} > 512")
-            return
-        n_tiles, Cs = -(-int(m.V) // VB), int(m.C)
-        k = max(1, min(cu // n_tiles, -(-Cs // 16)))      # one round, one workgroup per CU
-        m.ctx_ckb = min(256, -(-(-(-Cs // k)) // 16) * 16)
-        m.ctx_kb = -(-Cs // m.ctx_ckb)
-        m.ctx_fused = 1
-        aligned = self.flat.slots["inf_net.adapt_bert.weight"].offset % 4 == 0
-        why = [w for ok, w in (
-            (self.lib.gfk_smem_required(C.byref(m), 8) <= LDS_LIMIT, "LDS plan exceeds 160 KiB"),
-            (int(m.H[0]) <= 512, f"H0 = {int(m.H[0])} > 512"),
-            (Cs % 4 == 0, f"contextual_size = {Cs} is not a multiple of 4"),
-            (aligned, "adapt_bert is not 16-byte aligned in the flat buffer")) if not ok]
-        if why:
-            m.ctx_fused, m.ctx_kb = 0, 0
-            self._ctx_fallback("; ".join(why))
 
     def _ctx_fallback(self, why: str):
         """Leave the fused contextual kernels for host-issued hipBLASLt GEMMs (gradient
@@ -907,7 +501,7 @@ class FusedEngine(EngineBase):
             # precomputed logit-gradient tiles [n_tiles][B][66] (bwd_pre; + the pipelined
             # backward's store sinks, 64 floats per workgroup)
             # (the large-batch plan: the [B, ldb] logit / logit-gradient matrix)
-            "dt": f(B * int(m.ldb) if m.stage_flags & STAGE_LB and (m.lb_fused & 3) != 3 else
+            "dt": f(B * int(m.ldb) if plan.lb_library_gemms(m) else
                     m.n_tiles * B * 66 + 64 * (4 * m.n_dpart + 32) if m.bwd_pre else 1),
             # the large-batch plan's posterior column statistics (6 x 2K floats)
             "colstat": f(12 * K if m.stage_flags & STAGE_LB else 1),
@@ -1035,52 +629,18 @@ class FusedEngine(EngineBase):
 
     @property
     def ctx_gemm_dtype(self) -> Optional[str]:
-        """Operand precision of CombinedTM's contextual GEMMs (adapt_bert and its input-layer
-        term) in the forward: "bf16" where matmul_dtype = "bf16" runs the register-streamed
-        kernel (csrc/ctx.hip gfk_ctx_fwd_rs_k<BF>), else "fp32"; None without them."""
-        m = self._m
-        if not self.ctx_fused or m.ctx_fused != 1:
-            return None
-        rs = STAGE_CTX_FULL | STAGE_CTX_RS
-        return "bf16" if m.mm_bf16 and (m.stage_flags & rs) == rs else "fp32"
+        """Operand precision of CombinedTM's contextual GEMMs (plan.ctx_gemm_dtype)."""
+        return plan.ctx_gemm_dtype(self._m)
 
     @property
     def gemm_dtypes(self) -> Dict[str, Optional[str]]:
-        """Operand precision of each GEMM of the step, as the launchers choose it (read-only; it
-        restates csrc/prodlda.hip gfk_launch_prodlda_fwd / _bwd, csrc/neurallda.hip and
-        ``ctx_gemm_dtype``): "dec_fwd" (ProdLDA theta_d beta; NeuralLDA theta_d beta_sm),
-        "dthetad" (ProdLDA dlogit beta^T, both operands; NeuralLDA g beta_sm^T, beta_sm only),
-        "dbeta" (ProdLDA theta_d^T dlogit; NeuralLDA g^T theta_d), "ctx_a" / "ctx_z0"
-        (CombinedTM's x_ctx Wa^T and A Wc^T; None without them).  matmul_dtype = "bf16" rounds
-        them all except: the pipelined ProdLDA backward keeps fp32 operands in both its GEMMs;
-        the large-batch ProdLDA plan has no bf16 instance at all (NeuralLDA's kernels read
-        mm_bf16 themselves, at any batch size); the contextual GEMMs round only in the
-        register-streamed forward."""
-        m = self._m
-        on = bool(m.mm_bf16)
-        prod = m.kind == abi.KIND_PRODLDA
-        if prod and self.large_batch:
-            on = False
-        bwd = on
-        if on and prod:
-            kq4 = m.n_dpart < m.n_tiles and -(-int(m.K) // 16) >= 4
-            pipe = (kq4 and m.bwd_pre == 3 and m.bmax == 64 and m.ldb % 64 == 0
-                    and int(m.K) * int(m.ldb) * 4 < 0x7FFF0000)
-            bwd = not pipe
-        name = lambda b: "bf16" if b else "fp32"  # noqa: E731
-        ctx = self.ctx_gemm_dtype
-        return {"dec_fwd": name(on), "dthetad": name(bwd), "dbeta": name(bwd),
-                "ctx_a": ctx, "ctx_z0": ctx}
+        """Operand precision of each GEMM of the step (plan.gemm_dtypes)."""
+        return plan.gemm_dtypes(self._m)
 
     @property
     def launch_plan(self) -> str:
         """The launch plan in one phrase (recorded in bench / metrics records)."""
-        if self.large_batch:
-            if self._m.kind == abi.KIND_PRODLDA and (self._m.lb_fused & 3) != 3:
-                return ("large-batch: HIP kernels + hipBLASLt decoder GEMMs"
-                        + (" (backward)" if self._m.lb_fused else "") + ", gradient mode")
-            return "large-batch: HIP kernels, gradient mode"
-        return "fused kernels" + (" (fused optimizer epilogues)" if self.update_mode == UPDATE_FUSED else "")
+        return plan.launch_plan(self._m, self.update_mode)
 
     def set_fedavg_scale(self, w: Optional[float]):
         """Pre-scale the shared state by w after the update (None disables)."""
@@ -1185,25 +745,7 @@ class FusedEngine(EngineBase):
         self._invalidate_graph()
 
     def phases(self) -> List[int]:
-        if self._m.kind == abi.KIND_LDA:
-            ph = [p for p in abi.LDA_STEP if p != abi.PH_ADAM] + \
-                ([abi.PH_ADAM] if self.update_mode == UPDATE_GRAD else [])
-        else:
-            ph = abi.PRODLDA_STEP + ([abi.PH_ADAM] if self.update_mode == UPDATE_GRAD else [])
-            if self.large_batch:                    # the decoder's GEMMs around its kernels
-                if not self._m.lb_fused & 1:
-                    ph.insert(ph.index(abi.PH_PRODLDA_FWD), abi.PH_LB_GEMM_FWD)
-                if not self._m.lb_fused & 2:
-                    ph.insert(ph.index(abi.PH_PRODLDA_BWD) + 1, abi.PH_LB_GEMM_BWD)
-            if self._m.stage_flags & STAGE_FWD_POSTFOLD:
-                ph.remove(abi.PH_POST_FWD)          # computed by the strip forward
-        if self.ctx_fused:
-            if self._m.ctx_fused == 1:
-                ph.insert(ph.index(abi.PH_ENC_FWD), abi.PH_CTXF_FWD)
-                ph.insert(ph.index(abi.PH_ENC_BWD), abi.PH_CTXF_BWD)
-        elif self.kind == "ctm":
-            ph.insert(ph.index(abi.PH_ENC_FWD), abi.PH_CTX_FWD)
-            ph.insert(ph.index(abi.PH_ENC_BWD) + 1, abi.PH_CTX_BWD)
+        ph = plan.step_phases(self._m, self.update_mode)
         if self._comm is not None and self._comm["mode"] == "graph":
             if "beta" in self._comm:
                 last = abi.PH_PRODLDA_BWD if abi.PH_PRODLDA_BWD in ph else abi.PH_LDA_BETA_BWD
@@ -1387,7 +929,7 @@ class FusedEngine(EngineBase):
     def _alloc_ctx(self):
         """Buffers of the CTM contextual path (reference ctm inference_network.py:97-193)
         when it runs on host-issued GEMMs.  The default path is the fused kernels
-        (_plan_ctx: CombinedTM's ctx_fwd / ctx_bwd in csrc/ctx.hip, ZeroShotTM's dense
+        (ops/plan.py: CombinedTM's ctx_fwd / ctx_bwd in csrc/ctx.hip, ZeroShotTM's dense
         input layer in enc_in / win_update); these buffers serve (a) the fallback for
         shapes outside the kernels' plan (C % 4, H0 > 512, LDS, alignment -- logged by
         _ctx_fallback), where adapt_bert [B,C]x[C,V], the contextual half of
@@ -1709,8 +1251,8 @@ class FusedEngine(EngineBase):
     @property
     def host_gemm_fallback(self) -> bool:
         """True when part of the step runs as host-issued library GEMMs: the CTM contextual
-        path outside the fused ctx kernels' plan (_plan_ctx), or the large-batch plan's
-        decoder (_plan_large_batch)."""
+        path outside the fused ctx kernels' plan, or the large-batch plan's
+        decoder (ops/plan.py)."""
         return (self.kind == "ctm" and not self.ctx_fused) or self.large_batch
 
     def _warm_host_gemms(self):
@@ -1936,119 +1478,29 @@ class BatchedSteps:
 
     def _refresh(self):
         M = len(self.engines)
+        e0 = self.engines[0]
+        # the batched plan (ops/plan.py), once: validate() made the clients' shapes equal
+        bp = plan.plan_batched(e0.lib, e0._m, M, self._cu, plan.Knobs.from_env(), e0._u.n_w,
+                               e0._u.n_v, e0.update_mode, e0.postfold_ok, e0.phases())
         ms, us = [], []
         for e in self.engines:
             mm = abi.GfkModel.from_buffer_copy(bytes(e._m))
             mm.dev, mm.dev_upd, mm.n_batch = self._arr_m.data_ptr(), self._arr_u.data_ptr(), M
-            # the strip forward: M clients' tiles in one launch of 16-wave workgroups (one per
-            # CU).  The strips are grid-strided (a workgroup's wave group g takes tiles
-            # g grid + x, so any grid works): where M clients' one-tile-per-workgroup grids
-            # exceed one round of the CUs, each workgroup takes T whole tiles (one strip per
-            # wave), T the FEWEST in 1..4 whose M ceil(n_tiles / T) workgroups still fit one
-            # round -- T = 3 at M = 8, V = 4.7k: 192 workgroups of 12 busy waves instead of
-            # 144 of 16; past 4 tiles the M clients share one round (dec_grid = CUs / M).
-            # NeuralLDA's decoder kernels (beta forward / backward, grid-strided over the
-            # tiles) likewise: T tiles per workgroup so the M clients' workgroups fit one
-            # round of the CUs -- the backward's theta_d staging is then paid once per T
-            # tiles (8 clients, V = 4.7k: 0.1426 -> 0.1407 ms, same bits; one round of two
-            # workgroups per CU measured 0.1497, profiles/r6/lda/ab_batch_fill.txt).
-            # GFEDNTM_BATCH_STRIP=keep: the engines' own grids (rounds of the CUs).
-            if ((mm.stage_flags & STAGE_FWD_STRIP or mm.kind == abi.KIND_LDA)
-                    and M > 1 and M * mm.dec_grid > self._cu
-                    and os.environ.get("GFEDNTM_BATCH_STRIP", "fill") != "keep"):
-                t = next((t for t in (1, 2, 3, 4) if M * -(-mm.n_tiles // t) <= self._cu), None)
-                mm.dec_grid = -(-mm.n_tiles // t) if t else max(1, self._cu // M)
-            # the posterior folded into the strip forward for M > 1 clients (the engines' own
-            # plan keeps post_fwd for one client; GFEDNTM_POSTFOLD=0: never)
-            if (M > 1 and getattr(e, "_postfold_ok", False) and mm.stage_flags & STAGE_FWD_STRIP
-                    and os.environ.get("GFEDNTM_POSTFOLD", "auto") != "0"):
-                mm.stage_flags |= STAGE_FWD_POSTFOLD
-            # post_bwd: M clients x (bmax + 1) workgroups of 16 waves with the batch matrices
-            # in LDS (~93 KB: one per CU) run in three rounds at M = 8.  Two rows per
-            # workgroup (the matrices, weights and column sums staged once for both) and the
-            # batch-level workgroup moved into row_bwd: M bmax / 2 workgroups, one round
-            # (M (bmax + 1) <= CUs: the one-row shape).  Round 6 removed the opt-in variants
-            # measured slower: the matrices read from L2, and the persistent one-range
-            # backward walking several tiles (profiles/r5/ab_batch.txt).
-            # GFEDNTM_POST_ROWS = auto | serial2 | 2 | 4: the rows of a workgroup one after the
-            # other (serial2) or through each phase together (2 / 4 rows, bits 21 / 22; the
-            # own-row vectors of all rows in LDS: gfk_setup raises the kernels' limit)
-            knob = os.environ.get("GFEDNTM_POST_ROWS", "auto")
-            post = post_rows_flags(M, mm.bmax, self._cu, knob)
-            if post & STAGE_POST_JOINT:
-                mm.stage_flags |= post
-                if e.lib.gfk_smem_required(C.byref(mm), 4) > LDS_LIMIT:
-                    if knob != "auto":
-                        raise RuntimeError(f"GFEDNTM_POST_ROWS={knob}: the rows' vectors do not fit the LDS")
-                    mm.stage_flags &= ~(STAGE_POST_JOINT | STAGE_POST_ROWS4)
-                else:
-                    rc = e.lib.gfk_setup(C.byref(mm))
-                    if rc:
-                        raise RuntimeError(f"gfk_setup failed ({rc})")
-            mm.stage_flags |= post & STAGE_POST_ROWS2
-            # CombinedTM: M clients' vocabulary tiles in one launch fill the CUs the way one
-            # client's do at a large vocabulary, so the batched launch takes that plan -- the
-            # forward with all batch rows per tile (each Wa block staged once) and the
-            # persistent pipelined backward -- once M n_tiles > 2 CUs (V = 5k, 8 clients:
-            # 0.5296 -> 0.5175 / 0.5137 ms each, profiles/r6/ctm_batched/).  The z0 partials
-            # keep the per-tile layout (no register-streamed forward here).
-            # GFEDNTM_CTX_FULL / GFEDNTM_CTX_BWDPP = 0: the engines' own plan.
-            if (M > 1 and mm.ctx_fused == 1 and mm.bmax <= 64 and int(mm.H[0]) <= 64
-                    and M * mm.n_tiles > 2 * self._cu):
-                ctx_new = False
-                if (not mm.stage_flags & STAGE_CTX_FULL
-                        and os.environ.get("GFEDNTM_CTX_FULL", "auto") == "auto"):
-                    mm.stage_flags |= STAGE_CTX_FULL
-                    ctx_new = True
-                if (not mm.stage_flags & STAGE_CTX_BWDPP
-                        and os.environ.get("GFEDNTM_CTX_BWDPP", "auto") == "auto"):
-                    mm.stage_flags |= STAGE_CTX_BWDPP
-                    mm.ctx_bgrid = int(self._cu)
-                    ctx_new = True
-                if ctx_new:                  # (the new kernels' dynamic-LDS limit)
-                    rc = e.lib.gfk_setup(C.byref(mm))
-                    if rc:
-                        raise RuntimeError(f"gfk_setup failed ({rc})")
-            # win_update: all clients' W_in tiles in one launch -> the 8-wave tile shape once
-            # they exceed two rounds of 16-wave workgroups
-            if M * (mm.n_tiles + 8) > 2 * self._cu:
-                mm.stage_flags |= STAGE_WIN_BATCH8
-            # prodlda_bwd: two 16-wave workgroups share a CU, so 8 clients x 74 tiles run as
-            # a round of 64 tiles per XCD and a second one of 10; three 8-wave workgroups
-            # per CU hold them all at once.  GFEDNTM_BWD_WAVES = auto | 16 | 8
-            tile_bwd = (mm.kind == abi.KIND_PRODLDA and not mm.stage_flags & STAGE_LB
-                        and abi.PH_PRODLDA_BWD in self.engines[0].phases())
-            mm.stage_flags |= bwd_batch8_flag(
-                M, mm.n_tiles, self._cu, bmax=mm.bmax, K=mm.K, bf16=bool(mm.mm_bf16),
-                kq=bwd_kq(mm.n_tiles, mm.n_dpart, mm.K) if tile_bwd else 0, bwd_pre=mm.bwd_pre,
-                lds_bytes=bwd8_lds_bytes(mm.bmax, mm.K, mm.kt),
-                knob=os.environ.get("GFEDNTM_BWD_WAVES", "auto"))
-            # win_update's 8-wave tile kernel needs more than the 64 VGPRs of 8 waves per SIMD;
-            # at 6 (80 VGPRs) three workgroups share a CU, enough where they hold every
-            # client's tiles and jobs at once.  GFEDNTM_WIN_WAVES = auto | 8 | 6
-            extra = mm.n_tiles if mm.ctx_fused == 1 else -(-mm.C // VB) if mm.ctx_fused == 2 else 0
-            mm.stage_flags |= win_waves_flag(
-                M, mm.n_tiles + extra + e._u.n_w + e._u.n_v + 1, self._cu,
-                dense=not mm.stage_flags & (STAGE_WIN_SPARSE | STAGE_LB) and mm.bmax <= 128,
-                batch8=bool(mm.stage_flags & STAGE_WIN_BATCH8),
-                fused=e.update_mode == UPDATE_FUSED, H0=int(mm.H[0]),
-                lds_bytes=int(e.lib.gfk_smem_required(C.byref(mm), 5)),
-                knob=os.environ.get("GFEDNTM_WIN_WAVES", "auto"))
+            mm.stage_flags, mm.dec_grid, mm.ctx_bgrid = bp.stage_flags, bp.dec_grid, bp.ctx_bgrid
             uu = e._u
             if self._shared is not None:
                 uu = abi.GfkUpdate.from_buffer_copy(bytes(e._u))
                 self._point_at_shared(e, mm, uu)
             ms.append(bytes(mm))
             us.append(bytes(uu))
-        # the phases of the batched plan: post_fwd out where the launch folds it, back in
-        # where the launch dropped the engines' fold
-        ph = list(self.engines[0].phases())
-        folded = bool(abi.GfkModel.from_buffer_copy(ms[0]).stage_flags & STAGE_FWD_POSTFOLD)
-        if folded and abi.PH_POST_FWD in ph:
-            ph.remove(abi.PH_POST_FWD)
-        elif not folded and abi.PH_PRODLDA_FWD in ph and abi.PH_POST_FWD not in ph:
-            ph.insert(ph.index(abi.PH_PRODLDA_FWD), abi.PH_POST_FWD)
-        self._phases = ph
+        self._host = abi.GfkModel.from_buffer_copy(ms[0])
+        if bp.setup_flags is not None:       # kernels the engines' own plans did not set up
+            mm = abi.GfkModel.from_buffer_copy(ms[0])
+            mm.stage_flags = bp.setup_flags
+            rc = e0.lib.gfk_setup(C.byref(mm))
+            if rc:
+                raise RuntimeError(f"gfk_setup failed ({rc})")
+        self._phases, self.plan = bp.phases, bp.text
         blob = b"".join(ms) + b"".join(us)
         if blob != self._blob:
             if torch.cuda.is_current_stream_capturing():
@@ -2056,18 +1508,6 @@ class BatchedSteps:
             self._arr_m.copy_(torch.frombuffer(bytearray(b"".join(ms)), dtype=torch.uint8))
             self._arr_u.copy_(torch.frombuffer(bytearray(b"".join(us)), dtype=torch.uint8))
             self._blob = blob
-        self._host = abi.GfkModel.from_buffer_copy(ms[0])
-        # the shapes this launch runs, for records: "8 clients per launch; prodlda_bwd 8 waves"
-        self.plan = "%d clients per launch" % M
-        if abi.PH_PRODLDA_BWD in ph and not self._host.stage_flags & STAGE_LB:
-            self.plan += "; prodlda_bwd " + (
-                "8 waves" if self._host.stage_flags & STAGE_BWD_BATCH8 else
-                "16 waves" if bwd_kq(self._host.n_tiles, self._host.n_dpart, self._host.K) == 1
-                else "k ranges")
-        if (self._host.stage_flags & STAGE_WIN_BATCH8 and self._host.bmax <= 128
-                and not self._host.stage_flags & (STAGE_WIN_SPARSE | STAGE_LB)):
-            self.plan += "; win_update 8-wave tiles, %d waves per SIMD" % (
-                6 if self._host.stage_flags & STAGE_WIN_WAVES6 else 8)
 
     def prepare(self):
         """Upload the descriptors now (before a capture)."""
